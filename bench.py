@@ -15,6 +15,13 @@ all-reduce and SGD update.  Precision: float32 by default — the reference's
 
     python bench.py [--gpus N] [--steps K] [--warmup W]     # N>1: MirroredStrategy, one process, N GPUs
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...   # MWMS, one process per GPU
+
+A plain run sets up, warms up, times the K steps and prints the result line (a data-parallel run, N > 1,
+also hashes its replicas once after the timed region: its correctness invariant).  ``--full`` adds what the
+headline figure does not need: the K-step measurement repeated ``--repeats`` times (spread evidence,
+``config.repeat_ms_per_step``).  ``--dump-outputs DIR`` replays the timed execution once more after the
+measurements, from the seeded initial weights on the first batch group, and writes what it leaves — every
+model variable, and the loss and accuracy of its steps — as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -67,14 +74,55 @@ def parse():
     ap.add_argument("--gpus-per-worker", type=int, default=1,
                     help="mwms: local GPUs per worker process (torchrun --nproc-per-node = gpus / K)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="after the reported measurement, repeat the K-step measurement R times (spread only)")
+                    help="with --full: after the reported measurement, repeat the K-step measurement R times "
+                         "(spread only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the repeated measurements "
+                         "(--repeats; config.repeat_ms_per_step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the measurements, replay the timed execution once from the seeded initial weights on "
+                         "the first batch group and write what it leaves (every model variable, the loss and the "
+                         "accuracy of its steps) as DIR/<name>.npy: the same values in every run with these arguments")
     ap.add_argument("--devices", default=None,
                     help="mirrored: explicit local device list, e.g. 0,1,2,3 (0,0 = a 2-replica rehearsal on one GPU)")
     return ap.parse_args()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_outputs(prog):
+    """Device-side copies of replica 0's variables (trainable and BatchNorm moving statistics) and of its metric
+    accumulators [loss sum, correct, count, -]: what a caller of the training step gets back."""
+    plan = prog.plans[0]
+    st = plan.store
+    return [(nm, st.view(nm).detach().clone()) for nm in st.order], plan.metrics.detach().clone()
+
+
+def write_outputs(dirname, snap):
+    """DIR/<variable>.npy (float32; '/' in a variable name becomes '.') plus loss.npy and accuracy.npy (float64).
+    Above DUMP_LIMIT_BYTES in all, every variable is cut to the same fixed, seeded sample of its elements."""
+    import numpy as np
+    variables, metrics = snap
+    os.makedirs(dirname, exist_ok=True)
+    arrays = [(nm.replace("/", "."), t.float().cpu().numpy()) for nm, t in variables]
+    total = sum(v.nbytes for _, v in arrays)
+    if total > DUMP_LIMIT_BYTES - 4096:
+        keep = (DUMP_LIMIT_BYTES - 4096) / total
+        rng = np.random.default_rng(20240229)
+        arrays = [(nm, v.reshape(-1)[np.sort(rng.choice(v.size, max(1, int(v.size * keep)), replace=False))])
+                  for nm, v in arrays]
+    for nm, v in arrays:
+        np.save(os.path.join(dirname, nm + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    m = metrics.double().cpu().numpy()
+    np.save(os.path.join(dirname, "loss.npy"), np.float64(m[0] / m[2]))
+    np.save(os.path.join(dirname, "accuracy.npy"), np.float64(m[1] / m[2]))
+
+
 def main():
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.gpus is None:
         a.gpus = len(a.devices.split(",")) if a.devices else 1
     if a.no_graph:
@@ -137,6 +185,7 @@ def main():
                       steps_per_execution=spe)
     ncls = model.output_shape[-1]
     prog = model._program("train", GB)
+    w_init = model.get_weights() if a.dump_outputs else None
     dev = strategy.local_devices[0]
     in_shape = prog.x_shape
     # Synthetic MNIST-shaped data resident on the device: a pool of batches,
@@ -215,8 +264,8 @@ def main():
 
     try:
         elapsed = timed(n_warm)
-        # spread evidence (outside the reported measurement): the same K-step measurement repeated
-        repeats = [timed(n_warm + n_exec * (r + 1)) for r in range(max(0, a.repeats))]
+        # --full: spread evidence (outside the reported measurement): the same K-step measurement repeated
+        repeats = [timed(n_warm + n_exec * (r + 1)) for r in range(max(0, a.repeats))] if a.full else []
     finally:
         gc.enable()
     logs = tde.metrics.logs_from(prog.global_metrics(), ["accuracy"])
@@ -230,6 +279,23 @@ def main():
         same = all(f[2] == fps[0][2] for f in fps)   # trainable weights (BN moving stats are per replica)
         if strategy.worker_index == 0:
             print(f"[bench] replicas_identical={same}", file=sys.stderr, flush=True)
+    snap = None
+    if a.dump_outputs:
+        # What the timed path computes, comparable from run to run and from build to build: the weights after
+        # the timed steps are not (the warm-up runs a number of executions that depends on the clock, and the
+        # fused plans sum with float atomics, whose rounding a long training run amplifies), so the timed
+        # execution is replayed once more (the same program, the same hipGraph, its steps_per_execution steps)
+        # from the seeded initial weights, a zeroed step counter and zeroed metrics on the first batch group.
+        prog.sync()
+        model.set_weights(w_init)
+        for p in prog.plans:
+            p.iterations.zero_()
+        prog.reset_metrics()
+        prog.sync()
+        stage(0)
+        run_exec(0, prefetch=False)
+        prog.sync()
+        snap = snapshot_outputs(prog)
     # where the optimizer update runs: fused into the step's kernels (1 replica), into the xGMI
     # gradient all-reduce (one replica per process), or its own multi-tensor launch
     placement = {"local": "in_step_kernels", "xgmi": "allreduce"}.get(prog.plans[0].step_mode, "separate")
@@ -240,6 +306,8 @@ def main():
     ms = elapsed / a.steps * 1e3
     ips = GB * a.steps / elapsed
     if strategy.worker_index == 0:
+        if snap is not None:
+            write_outputs(a.dump_outputs, snap)
         print(f"[bench] plan={prog.plan_kind} graph={prog.use_graph} spe={spe} world={n} local={n_local} "
               f"loss={logs['loss']:.4f} acc={logs['accuracy']:.4f}", file=sys.stderr)
         print(json.dumps({
@@ -256,7 +324,8 @@ def main():
                        "optimizer": f"SGD(lr={a.lr})", "plan": prog.plan_kind,
                        "allreduce": ar,
                        "hipgraph": prog.use_graph, "grad_buckets": len(prog.buckets or prog.group_buckets or []) or 1,
-                       # the same K-step measurement repeated after the reported one (ms/step; spread evidence)
+                       # --full: the same K-step measurement repeated after the reported one (ms/step; spread
+                       # evidence); empty in a plain run
                        "repeat_ms_per_step": [round(r / a.steps * 1e3, 5) for r in repeats],
                        "optimizer_placement": placement,
                        # fused_push: the backward stores the Dense(64) weight gradient straight into the
