@@ -9,9 +9,11 @@
 //
 // The f32 MFMA issues at 1/16 of the bf16 rate (MI355X_MICROARCH.md § Matrix cores), so the work
 // per workgroup is cut to keep each CU's matrix pipe time small and spread over more CUs:
-//   forward   FPW=1 pooled position x 64 images per workgroup (169 workgroups for MNIST);
-//             wave w owns the output column tile w of all 4 row tiles (4 independent
-//             accumulators, 32 MFMAs), split-K atomics into hpre as in the bf16 form;
+//   forward   4 consecutive pooled positions x 16 images per workgroup (43 x 4 = 172 workgroups
+//             for MNIST at batch 64); wave w owns the output column tile w over K = 4 x 32 (one
+//             accumulator per position, 32 MFMAs, summed in registers), then split-K atomics into
+//             hpre: 4 wave-instructions per wave, a quarter of the float-atomic bytes of one
+//             position per workgroup (the adds run at ~1.3 TB/s chip-wide whatever their spread);
 //   backward  ONE pooled position per workgroup (169 + the head workgroup); per 64-image chunk
 //             waves 0-7 compute dP = G . W1^T (8 tiles x 16 MFMAs) while waves 8-15 compute
 //             the position's dW1 rows = P^T . G (8 tiles x 16 MFMAs), then all 16 waves run the
@@ -21,59 +23,84 @@
 // Fragment map of the 16x16x4 f32 MFMA: lane l holds A[l&15][k] and B[k][l&15] with k set by
 // (l>>4, step); a lane's k for step s of a 16-k group is fq*16 + 4*((s/4 + fq) & 3) + s%4
 // (fq = l>>4), so each lane reads its operands as float4 rows and, with 72-float LDS rows
-// (40 for the 32-wide forward tile, 8-k groups), the ds_read_b128 lane groups hit disjoint
-// banks (searched exhaustively over strides and per-group rotations).
+// (168 = 40 mod 64 for the forward's 128-wide tile, 8-k groups per position: a position's column
+// offset shifts every lane's bank alike), the ds_read_b128 lane groups hit disjoint banks (searched
+// exhaustively over strides and per-group rotations).
 #include "tde_convnet.h"
 
 namespace tde {
 using namespace cnet;
 
-constexpr int PS32 = 40;   // f32 LDS row stride of the forward's pooled tile [64][32]
+constexpr int FG = 4;      // pooled positions per forward workgroup
+constexpr int FB = 16;     // images per forward workgroup
+constexpr int AS32 = 168;  // f32 LDS row stride of the forward's pooled tile [FB][FG*32]
 constexpr int GS32 = 72;   // f32 LDS row stride of the backward's 64-wide operand rows
 constexpr int DPS32 = 40;  // f32 LDS row stride of dP [64][32]
+static_assert(FG == 4 && FB == 16, "the forward's lane maps are written for 4 positions x 16 images");
 
-constexpr int fwd32_lds(int fpw) { return fpw * 64 * PS32 * 4 + kXrBytes + kConvW * 4; }
+// per-image stride of the forward's staged rows: 4 (mod 64) floats, so the float2 patch reads of a
+// ds_read_b64 lane group (16 images x 2 consecutive positions, 2 floats apart) cover the 64 banks once
+__host__ __device__ constexpr int fwd32_istride(int W) { return XR * W + ((4 - (XR * W) % 64) + 64) % 64; }
+constexpr int kXr32Bytes = FB * (XR * XW + 64) * 4;
+constexpr int kFwd32Lds = FB * AS32 * 4 + kXr32Bytes + kConvW * 4;
 
 // column of the float4 a lane reads for group i of a 32-wide (8 k per lane group) row
 __device__ __forceinline__ int k8_col(int fq, int i) { return fq * 8 + 4 * ((i + fq) & 1); }
 // ... and of a 64-wide (16 k per lane group) row
 __device__ __forceinline__ int k16_col(int fq, int i) { return fq * 16 + 4 * ((i + fq) & 3); }
 
-template <int FPW>
-__global__ __launch_bounds__(FPW * 256) void convnet32_fwd_kernel(FwdArgs a) {
-  constexpr int NT = FPW * 256;
+// The <= XR input rows of the workgroup's FB images -> xr (coalesced float4 loads, all issued before
+// the first LDS store: one round trip; the 16-byte-aligned image stride takes whole float4 stores).
+__device__ __forceinline__ void fwd32_stage_x(const FwdArgs& a, float* xr, int b0, int py0, int nrows) {
+  const int W = a.W, H = a.H;
+  const int istride = fwd32_istride(W);
+  const int n4 = nrows * W / 4;  // float4 per image
+  constexpr int kU = 3;          // 16 images x 6 rows x 32 floats = 768 float4: one pass of 256 threads
+  for (int i0 = threadIdx.x; i0 < FB * n4; i0 += kU * 256) {
+    float4 v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u * 256, bl = i / n4, q = i - bl * n4;
+      v[u] = float4{0.f, 0.f, 0.f, 0.f};
+      if (i < FB * n4 && b0 + bl < a.B)
+        v[u] = *reinterpret_cast<const float4*>(a.x + (size_t)(b0 + bl) * H * W + (size_t)(2 * py0) * W + q * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int i = i0 + u * 256, bl = i / n4, q = i - bl * n4;
+      if (i < FB * n4) *reinterpret_cast<float4*>(xr + bl * istride + q * 4) = v[u];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
+  constexpr int NT = 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
-  float* Ps = reinterpret_cast<float*>(fsm);                                        // [FPW][64][PS32]
-  float* xr = reinterpret_cast<float*>(fsm + FPW * 64 * PS32 * 4);                  // [64][XR][W]
-  float* wcs = reinterpret_cast<float*>(fsm + FPW * 64 * PS32 * 4 + kXrBytes);      // [10][CC]
+  float* As = reinterpret_cast<float*>(fsm);                                  // [FB][AS32] pooled tile
+  float* xr = reinterpret_cast<float*>(fsm + FB * AS32 * 4);                  // [FB][XR][W]
+  float* wcs = reinterpret_cast<float*>(fsm + FB * AS32 * 4 + kXr32Bytes);    // [10][CC]
   stamp(a.stamps, 0);
   if (a.inc_iter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.inc_iter, 1ull);
   if (a.fly_count && a.pend && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && *a.pend)
     atomicAdd(a.fly_count, 1ull);
   fwd_snap_head(a, NT);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
   const int W = a.W, H = a.H;
   const int Wp = (W - 2) / 2, Hp = (H - 2) / 2, P = Hp * Wp;
-  const int p0 = blockIdx.x * FPW;
-  const int b0 = blockIdx.y * 64;
-  const int b = b0 + lane;
-  const bool bok = b < a.B;
-  const int pp = __builtin_amdgcn_readfirstlane(wave >> 2), cg = __builtin_amdgcn_readfirstlane(wave & 3),
-            c0 = cg * 8;
-  const int p = p0 + pp;
-  const bool pok = p < P;
-  const int py0 = p0 / Wp;
+  const int p0 = blockIdx.x * FG;
+  const int b0 = blockIdx.y * FB;
+  const int py0 = p0 / Wp;   // FG <= Wp (host check): the group's positions lie in pooled rows py0, py0 + 1
   const int nrows = min(XR, H - 2 * py0);
   const float* W1 = reinterpret_cast<const float*>(a.W1);
   float* Pt = reinterpret_cast<float*>(a.Pt);
 
   // B fragments first (independent of the staging below, so their round trip overlaps it):
   // W1[kp*32 + k][nt*16 + fr] for this lane's 8 k of each position (f32 master, [K][HD])
-  const int nt = wave & 3;
-  float wfr[FPW][8];
+  const int nt = wave;
+  float wfr[FG][8];
 #pragma unroll
-  for (int ks = 0; ks < FPW; ++ks) {
+  for (int ks = 0; ks < FG; ++ks) {
     const int kp = p0 + ks;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -81,19 +108,22 @@ __global__ __launch_bounds__(FPW * 256) void convnet32_fwd_kernel(FwdArgs a) {
       for (int j = 0; j < 4; ++j)
         wfr[ks][4 * i + j] = kp < P ? W1[(size_t)(kp * CC + k8_col(fq, i) + j) * a.ldw1 + nt * 16 + fr] : 0.f;
   }
-  fwd_stage_x(a, xr, b0, py0, nrows, NT);
+  fwd32_stage_x(a, xr, b0, py0, nrows);
   fwd_stage_conv(a, wcs, NT);
   stamp(a.stamps, 1);
   lds_barrier();
+
+  // ---- phase 1: conv + bias + ReLU + 2x2 max-pool; lane = (image fr, position slot fq), wave = 8 channels
+  const int cg = wave, c0 = cg * 8;
   ConvW8 cw;
   cw.load(wcs, c0);
-
-  // ---- phase 1: conv + bias + ReLU + 2x2 max-pool for 8 channels (f32 tile, f32 P^T)
+  const int p = p0 + fq, b = b0 + fr;
+  const bool pok = p < P, bok = b < a.B;
   float out[8];
   if (bok && pok) {
     const int py = p / Wp, px = p - py * Wp;
     uint64_t packed;
-    conv_pool8(xr + lane * fwd_istride(W) + (2 * (py - py0)) * W + 2 * px, W, cw, out, packed);
+    conv_pool8(xr + fr * fwd32_istride(W) + (2 * (py - py0)) * W + 2 * px, W, cw, out, packed);
     if (a.amax) a.amax[((size_t)p * (CC / 8) + cg) * a.lda + b] = packed;
   } else {
 #pragma unroll
@@ -104,7 +134,7 @@ __global__ __launch_bounds__(FPW * 256) void convnet32_fwd_kernel(FwdArgs a) {
     for (int cc = 0; cc < 8; ++cc) Pt[(size_t)(p * CC + c0 + cc) * a.ldPt + b] = out[cc];
   }
   {
-    float* dst = Ps + ((size_t)pp * 64 + lane) * PS32 + c0;
+    float* dst = As + fr * AS32 + fq * CC + c0;
     *reinterpret_cast<float4*>(dst) = float4{out[0], out[1], out[2], out[3]};
     *reinterpret_cast<float4*>(dst + 4) = float4{out[4], out[5], out[6], out[7]};
   }
@@ -112,38 +142,31 @@ __global__ __launch_bounds__(FPW * 256) void convnet32_fwd_kernel(FwdArgs a) {
   lds_barrier();
   stamp(a.stamps, 3);
 
-  // ---- phase 2: hpre[64 x 64] += Ps(64 x FPW*32) . W1(FPW*32 x 64) on the f32 MFMA; wave = column
-  // tile nt of row tiles mt = (wave>>2) + FPW*j (independent accumulators keep the pipe issuing)
-  constexpr int NMT = 4 / FPW;
+  // ---- phase 2: hpre[16 x 64] += As(16 x FG*32) . W1(FG*32 x 64) on the f32 MFMA; wave = column tile nt,
+  // one accumulator per position (independent chains keep the pipe issuing), summed before the adds:
+  // the FG positions' split-K partial sums meet in registers, not in memory
   float* const hrow = a.hpre + (size_t)(blockIdx.x % a.hrep) * a.hrep_stride;
-  f32x4 acc[NMT];
+  f32x4 acc[FG];
 #pragma unroll
-  for (int j = 0; j < NMT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ks = 0; ks < FG; ++ks) acc[ks] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ks = 0; ks < FPW; ++ks) {
-    if (p0 + ks >= P) continue;
+  for (int i = 0; i < 2; ++i) {
+    float4 av[FG];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float4 av[NMT];
+    for (int ks = 0; ks < FG; ++ks)
+      av[ks] = *reinterpret_cast<const float4*>(As + fr * AS32 + ks * CC + k8_col(fq, i));
 #pragma unroll
-      for (int j = 0; j < NMT; ++j) {
-        const int mt = (wave >> 2) + FPW * j;
-        av[j] = *reinterpret_cast<const float4*>(Ps + ((size_t)ks * 64 + mt * 16 + fr) * PS32 + k8_col(fq, i));
-      }
+    for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int j = 0; j < NMT; ++j) acc[j] = mfma_f32x4(f4get(av[j], e), wfr[ks][4 * i + e], acc[j]);
-    }
+      for (int ks = 0; ks < FG; ++ks) acc[ks] = mfma_f32x4(f4get(av[ks], e), wfr[ks][4 * i + e], acc[ks]);
   }
+  // positions past P hold zeros on both sides (out = 0, wfr = 0): they add nothing
 #pragma unroll
-  for (int j = 0; j < NMT; ++j) {
-    const int mt = (wave >> 2) + FPW * j;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = b0 + mt * 16 + fq * 4 + r;
-      if (row < a.B) atomicAdd(hrow + (size_t)row * HD + nt * 16 + fr, acc[j][r]);
-    }
+  for (int r = 0; r < 4; ++r) {
+    const int row = b0 + fq * 4 + r;
+    // summed in position order, the order in which the consumers sum the replicas of the deterministic layout
+    const float s = ((acc[0][r] + acc[1][r]) + acc[2][r]) + acc[3][r];
+    if (row < a.B) atomicAdd(hrow + (size_t)row * HD + nt * 16 + fr, s);
   }
   stamp(a.stamps, 4);
 }
@@ -383,27 +406,12 @@ TDE_API int tde_convnet_fwd_f32(const float* x, const float* wc, const float* bc
   if (((uintptr_t)wc | (uintptr_t)bc | (uintptr_t)W1) & 15) return -2;
   if (opt && (!opt_ok(opt) || !opt->pend)) return -4;
   const int P = ((H - 2) / 2) * ((W - 2) / 2);
-  int by = (B + 63) / 64;
-  if (Pt) {
-    const int byp = (ldPt + 63) / 64;
-    if (byp > by) by = byp;
-  }
+  // image tiles: the padding columns B <= b < ldPt of Pt are written too (as zeros)
+  const int by = ((Pt && ldPt > B ? ldPt : B) + FB - 1) / FB;
   FwdArgs a{x, wc, bc, W1, ldw1, hpre, Pt, ldPt, (uint64_t*)amax, lda, B, H, W, stamps};
   fill_fwd_opt(a, opt, off_wc, off_bc, inc_iter, hrep, hrep_stride);
-  // positions per workgroup (TDE_CONVNET32_FPW = 1|2, default 1)
-  static const int fpw = [] {
-    const char* e = getenv("TDE_CONVNET32_FPW");
-    return (e && atoi(e) == 2) ? 2 : 1;
-  }();
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)convnet32_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd32_lds(1));
-    hipFuncSetAttribute((const void*)convnet32_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd32_lds(2));
-    attr_set = true;
-  }
-  const dim3 grid((P + fpw - 1) / fpw, by);
-  if (fpw == 1) convnet32_fwd_kernel<1><<<grid, 256, fwd32_lds(1), stream>>>(a);
-  else convnet32_fwd_kernel<2><<<grid, 512, fwd32_lds(2), stream>>>(a);
+  const dim3 grid((P + FG - 1) / FG, by);
+  convnet32_fwd_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;
 }
