@@ -1,0 +1,113 @@
+"""The float64 small-net oracle (tests/smallnet_oracle.py) against the repository's own fp32
+``ReferencePlan`` on the CPU, for every model and batch of tests/test_smallnet_forms_gpu.py.
+
+Validates, without a GPU: the oracle's padding and pool conventions (asymmetric TF ``same`` pads, floor
+pooling), the quantizer's exactness claim (fp32 conv trunk == float64 bit for bit, and the sum of |terms|
+below 2^24 grid steps) and the near-tie conditions on the Dense ReLU units and the head.
+
+fp32 reference vs float64, norm-wise relative, as printed by this test (run with -s; the figures move in
+the last digit with the CPU's conv / GEMM kernels).  Trunk exact everywhere; loss <= 1.1e-7, predict
+<= 2.8e-7.  headroom = 2^24 grid steps / largest sum of |terms|; near_tie, margin: see smallnet_oracle.
+  padded B=5/8        headroom 408, near_tie 0.038, margin 0.16
+      conv2d/kernel 1.2e-07, conv2d/bias 1.3e-07, conv2d_1/kernel 9.4e-08, conv2d_1/bias 6.3e-08,
+      conv2d_2/kernel 6.6e-08, conv2d_2/bias 6.8e-08, dense/kernel 6.4e-08, dense_1/kernel 1.4e-07,
+      dense_1/bias 1.1e-07
+  padded B=67/67      headroom 348, near_tie 0.0027, margin 0.070
+      conv2d/kernel 2e-07, conv2d/bias 2.2e-07, conv2d_1/kernel 1.2e-07, conv2d_1/bias 7.1e-08,
+      conv2d_2/kernel 7.8e-08, conv2d_2/bias 1.3e-07, dense/kernel 1.6e-07, dense_1/kernel 1e-07,
+      dense_1/bias 9.4e-08
+  wide_taps B=5/8     headroom 44, margin 0.031
+      conv2d/kernel 1.5e-07, conv2d/bias 1.4e-07, conv2d_1/kernel 9.5e-08, dense/kernel 4.6e-08, dense/bias 2.9e-08
+  wide_taps B=67/67   headroom 42, margin 0.0020
+      conv2d/kernel 2.6e-07, conv2d/bias 3.7e-07, conv2d_1/kernel 1.4e-07, dense/kernel 1.4e-07, dense/bias 1.1e-07
+  wide_out B=5/8      headroom 37, margin 0.094
+      conv2d/kernel 1.5e-07, conv2d/bias 1.6e-07, conv2d_1/kernel 1.2e-07, conv2d_1/bias 1e-07,
+      dense/kernel 6.9e-08, dense/bias 7e-08
+  wide_out B=67/67    headroom 35, margin 0.0073
+      conv2d/kernel 1.6e-07, conv2d/bias 2.7e-07, conv2d_1/kernel 2.3e-07, conv2d_1/bias 2.3e-07,
+      dense/kernel 1.3e-07, dense/bias 2.2e-07
+  wide_scratch B=5/8  headroom 1570, margin 0.013
+      conv2d/kernel 2.6e-07, conv2d/bias 2e-07, dense/kernel 2e-07, dense/bias 1.8e-07
+  wide_scratch B=67/67 headroom 1490, margin 0.013
+      conv2d/kernel 2.2e-07, conv2d/bias 9.8e-08, dense/kernel 1.4e-07, dense/bias 6.7e-08
+  lenet5 B=37/64      headroom 38, near_tie 3.4e-4 (Dense(120)), margin 0.0014
+      conv2d/kernel 4.8e-07, conv2d/bias 4.7e-07, conv2d_1/kernel 1.4e-07, conv2d_1/bias 1.2e-07,
+      dense/kernel 1.4e-07, dense/bias 1.2e-07, dense_1/kernel 1.6e-07, dense_1/bias 6.6e-08,
+      dense_2/kernel 2e-07, dense_2/bias 2.7e-08
+  lenet5_nobias B=37/64 headroom 34, near_tie 8.5e-4, margin 0.0031 (seed 2; seed 0 leaves a unit at 3.6e-5)
+      conv2d/kernel 5.1e-07, conv2d_1/kernel 3e-07, dense/kernel 2e-07, dense/bias 1.9e-07,
+      dense_1/kernel 3.1e-07, dense_1/bias 1.4e-07, dense_2/kernel 3.7e-07, dense_2/bias 9.1e-08
+  geo3 B=37/64        headroom 9280, margin 0.010
+      conv2d/kernel 7.4e-07, conv2d/bias 8.9e-07, dense/kernel 1e-07, dense/bias 1e-07
+  lenet5 randn (unquantized, the mask-effect step)
+      conv2d/kernel 3.8e-07, conv2d/bias 3.8e-07, conv2d_1/kernel 2.4e-07, conv2d_1/bias 1.8e-07,
+      dense/kernel 2.5e-07, dense/bias 1.4e-07, dense_1/kernel 2.6e-07, dense_1/bias 6.8e-08,
+      dense_2/kernel 2.6e-07, dense_2/bias 7.1e-08
+"""
+import pytest
+import torch
+
+import smallnet_oracle as O
+
+
+def test_models_are_smallnet_models():
+    """Every model is one ``match_smallnet`` accepts and no other fused plan's matcher takes first."""
+    import tensorflow_distributed_example_amd as tde
+    from tensorflow_distributed_example_amd.train import program as PG
+    from tensorflow_distributed_example_amd.train import smallnet as SN
+    for name in O.MODELS:
+        m, _ = O.build(tde, name, 5)
+        assert PG.match_convnet(m, m.loss) is None, name
+        spec = SN.match_smallnet(m, m.loss)
+        assert spec is not None, name
+        if name == "padded":     # the interior asymmetric pads the kernel sees only the top / left of
+            c3 = [s for s in spec if s["kind"] == SN.CONV][2]
+            assert (c3["pt"], c3["pb"], c3["pl"], c3["pr"]) == (0, 1, 1, 2)
+
+
+def test_grid_round():
+    assert O.grid_round([0.3, -0.3, 0.031], 4).tolist() == [0.3125, -0.3125, 0.0]
+
+
+@pytest.mark.parametrize("name,B,Bplan", O.CASES)
+def test_oracle_matches_fp32_reference(name, B, Bplan):
+    import tensorflow_distributed_example_amd as tde
+    m, x, y = O.make_case(tde, name, B, Bplan)
+    in_bits, w_bits = O.MODELS[name][2:]
+    exact, headroom = O.trunk_check(m, m._store, x, B, in_bits, w_bits)
+    orc = O.oracle(m, m._store, x, y, B, Bplan)
+    ref = O.reference_errors(tde, m, x, y, B, Bplan, orc)
+    tag = f"{name} B={B}/{Bplan}"
+    print(f"[{tag}] trunk_exact={exact} headroom={headroom:.3g} near_tie={orc['near_tie']:.3g} "
+          f"margin={orc['margin']:.3g} loss={ref['loss']:.2g} predict={ref['predict']:.2g}")
+    for n, e in ref["grads"].items():
+        print(f"[{tag}] grad {n}: {e:.2g}")
+    assert exact and headroom > 1.0
+    assert orc["near_tie"] > O.TIE and orc["margin"] > O.TIE
+    assert all(torch.isfinite(g).all() and g.abs().max() > 0 for g in orc["grads"].values())
+    assert set(orc["grads"]) == set(m._store.names(trainable=True))
+    for n, e in ref["grads"].items():
+        assert e < O.TOL, (n, e)
+    assert ref["loss"] < O.TOL and ref["eval_loss"] < O.TOL and ref["predict"] < O.TOL
+    assert ref["correct"] == ref["eval_correct"] == orc["correct"] and ref["count"] == B
+    assert orc["out"].shape == (B, m.output_shape[-1])
+    # the ReLU layers' pre-activations: one per ReLU, conv ones on the grid
+    nrelu = sum(getattr(l, "activation", None) == "relu" for l in m.layers)
+    assert len(orc["preacts"]) == nrelu
+    step = 2.0 ** -(in_bits + 3 * w_bits)
+    for kind, _, t in orc["preacts"]:
+        if kind == "relu_conv":
+            assert torch.equal(torch.round(t / step) * step, t)
+
+
+def test_oracle_randn_case_matches_fp32_reference():
+    """The unquantized LeNet-5 step of the mask-effect check."""
+    import tensorflow_distributed_example_amd as tde
+    B, Bplan = O.FAST_BATCH
+    m, x, y = O.make_case(tde, "lenet5", B, Bplan, data="randn")
+    orc = O.oracle(m, m._store, x, y, B, Bplan)
+    ref = O.reference_errors(tde, m, x, y, B, Bplan, orc)
+    for n, e in ref["grads"].items():
+        print(f"[lenet5 randn] grad {n}: {e:.2g}")
+        assert e < O.TOL, (n, e)
+    assert ref["loss"] < O.TOL and ref["predict"] < O.TOL
