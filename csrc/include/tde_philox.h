@@ -32,4 +32,18 @@ __device__ __forceinline__ float philox_keep(float rate, unsigned long long seed
   return ((w >> 8) * (1.f / 16777216.f) < keep) ? 1.f / keep : 0.f;
 }
 
+// The keep scales of elements 4 blk .. 4 blk + 3 from one Philox block: out[q] == philox_keep(.., 4 blk + q).
+__device__ __forceinline__ void philox_keep4(float rate, unsigned long long seed, long long it, int layer,
+                                             long long blk, float* out) {
+  const uint2 key{(unsigned)seed, (unsigned)(seed >> 32)};
+  const unsigned long long c = (unsigned long long)blk;
+  const uint4 r = philox(uint4{(unsigned)c, (unsigned)(c >> 32), (unsigned)it, (unsigned)layer}, key);
+  const float keep = 1.f - rate;
+  const float on = 1.f / keep;
+  out[0] = ((r.x >> 8) * (1.f / 16777216.f) < keep) ? on : 0.f;
+  out[1] = ((r.y >> 8) * (1.f / 16777216.f) < keep) ? on : 0.f;
+  out[2] = ((r.z >> 8) * (1.f / 16777216.f) < keep) ? on : 0.f;
+  out[3] = ((r.w >> 8) * (1.f / 16777216.f) < keep) ? on : 0.f;
+}
+
 }  // namespace tde

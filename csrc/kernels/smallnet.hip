@@ -11,7 +11,9 @@
 //                          (p - onehot) / global_batch into the logits buffer, then the backward in
 //                          place (every gradient overwrites the activation it belongs to, masked by
 //                          that activation's ReLU), per-image conv weight/bias gradients into `part`,
-//                          dense inputs and pre-activation gradients into `rec`.
+//                          dense inputs and pre-activation gradients into `rec`.  A Dropout layer is a
+//                          multiply of its owner's output in LDS by the Philox keep scale (forward) and of
+//                          the gradient that lands on that buffer by the regenerated scale (backward).
 //   smallnet_wgrad_kernel  batch reductions: conv partials summed over images, dense weight gradients
 //                          as X^T G over the batch on the exact-f32 MFMA, bias gradients, metrics; each gradient
 //                          element is finished by exactly one thread, which either stores it into the
@@ -22,10 +24,12 @@
 // distributed_with_keras.py:33-43, tf2_mnist_distributed.py:66-83); the per-step loss is
 // sum(CE) / global_batch (Keras AUTO reduction under a strategy).
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "tde_common.h"
 #include "tde_optim.h"
+#include "tde_philox.h"
 
 namespace tde {
 
@@ -44,6 +48,9 @@ struct SnLayer {
   int w_off, b_off;    // flat weight offsets (b_off < 0: no bias)
   int in, out, wl;     // LDS offsets: input, output, staged conv kernel (+ bias)
   int part, xo, go;    // conv: offset in the per-image partial record; dense: X / G offsets in `rec`
+  // Dropout on this layer's output (drop_rate: float bits, 0 = none): seed, layer id and the D = Ho Wo Co
+  // values per image of philox_keep(rate, seed, step, lid, b D + j)
+  int drop_rate, drop_seed_lo, drop_seed_hi, drop_lid, drop_n;
 };
 constexpr int kSnLayerInts = sizeof(SnLayer) / sizeof(int);
 
@@ -59,6 +66,8 @@ struct SnArgs {
   float* rec;
   float* metrics;
   long long* iterations;
+  const long long* step;  // steps completed before this one (written by the previous smallnet_wgrad_kernel);
+                          // null when no layer drops
   float scale;
   float* probs;
   int probs_softmax;
@@ -787,6 +796,26 @@ __device__ void sn_dense_bwd(const SnLayer L, float* s, const float* w, float* r
   }
 }
 
+// Dropout of layer L's output, or of the gradient w.r.t. it (the same buffer in the backward), in
+// place: row b of the [B, D] activation is elements b D .. b D + D - 1 of the layer's Philox stream, one
+// block per 4 consecutive elements -- b D need not be a multiple of 4, so the first and the last block
+// of a row straddle it and their words outside the row are dropped.
+__device__ void sn_drop(const SnLayer L, float* s, long long step, int b) {
+  float* v = s + L.out;
+  const float rate = __int_as_float(L.drop_rate);
+  const unsigned long long seed = (unsigned)L.drop_seed_lo | ((unsigned long long)(unsigned)L.drop_seed_hi << 32);
+  const long long e0 = (long long)b * L.drop_n, e1 = e0 + L.drop_n;
+  for (long long blk = (e0 >> 2) + threadIdx.x; 4 * blk < e1; blk += kSnThreads) {
+    float k[4];
+    philox_keep4(rate, seed, step, L.drop_lid, blk, k);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const long long e = 4 * blk + q;
+      if (e >= e0 && e < e1) v[e - e0] *= k[q];
+    }
+  }
+}
+
 template <typename F>
 __device__ __forceinline__ void sn_by_cg(int Co, F&& f) {
   if ((Co & 3) == 0) f(std::integral_constant<int, 4>{});
@@ -828,6 +857,9 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
   };
   stamp();
   float* rec = a.rec + (long long)b * a.nrec;
+  // one index for every workgroup of the step, forward and backward: `iterations` itself changes while
+  // the grid runs (block 0 above)
+  const long long step = a.step ? a.step[0] : 0;
   for (int l = 0; l < a.nl; ++l) {
     const SnLayer L = a.L[l];
     if (L.kind == kSnConv) {
@@ -838,6 +870,10 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
       sn_dense_fwd(L, s, a.w, scratch, rec, train);
     }
     __syncthreads();
+    if (train && L.drop_rate != 0) {  // before any consumer reads it (a Dense consumer records it for the wgrad)
+      sn_drop(L, s, step, b);
+      __syncthreads();
+    }
     stamp();
   }
   // softmax cross-entropy on the last layer's logits (one wave)
@@ -895,6 +931,10 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
   float* part = a.part + (long long)b * a.npart;
   for (int l = a.nl - 1; l >= 0; --l) {
     const SnLayer L = a.L[l];
+    if (L.drop_rate != 0) {  // the consumer left d loss / d dropped output in `out`
+      sn_drop(L, s, step, b);
+      __syncthreads();
+    }
     if (L.kind == kSnConv) {
       if (!sn_conv_fast(1, L, s, part, a.mfma))
         sn_by_cg(L.Co, [&](auto cg) { sn_conv_wgrad<decltype(cg)::value>(L, s, part); });
@@ -934,6 +974,7 @@ struct SnWgradArgs {
   float* m;
   float* v;
   const long long* iterations;
+  long long* step;  // optional: set to *iterations for the next step kernel's dropout masks
   float* metrics;
   OptHyper h;
 };
@@ -973,6 +1014,8 @@ __global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
       atomicAdd(&a.metrics[1], red[1][0] + red[1][1] + red[1][2] + red[1][3]);
       atomicAdd(&a.metrics[2], (float)a.B);
     }
+    // nothing writes `iterations` during this launch, so the next step kernel's workgroups all read one value
+    if (tid == 0 && a.step) a.step[0] = a.iterations[0];
     return;
   }
   if (blk < a.conv_blk0 + a.conv_nblk) {  // conv partials: 32 parameters x 8 image slices
@@ -1056,21 +1099,33 @@ TDE_API int tde_smallnet_limits(int* out) {
 }
 
 // layers: nl x kSnLayerInts int32 (SnLayer field order).  mode 0 train (part / rec written,
-// iterations += 1), 1 eval (metrics += loss, correct, count), 2 predict (probs).
+// iterations += 1), 1 eval (metrics += loss, correct, count), 2 predict (probs).  step: device word
+// holding the number of completed training steps, required when a layer drops (Dropout is the identity
+// in modes 1 and 2).
 TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const float* w, const float* x,
                               int x_stride, int in0, int n_in0, const int* img, const int* y, float* part, int npart,
                               float* rec,
-                              int nrec, float* metrics, long long* iterations, float scale, float* probs,
+                              int nrec, float* metrics, long long* iterations, const long long* step, float scale,
+                              float* probs,
                               int probs_softmax, long long* stamps, hipStream_t stream) {
   if (nl < 1 || nl > kSnMaxLayers || B <= 0) return -1;
   if (mode == 0 && (!part || !rec || !iterations || nrec < 2)) return -2;
   SnArgs a{};
+  bool drops = false;
   for (int l = 0; l < nl; ++l) {
     int* f = reinterpret_cast<int*>(&a.L[l]);
     for (int k = 0; k < kSnLayerInts; ++k) f[k] = layers[l * kSnLayerInts + k];
     const SnLayer L = a.L[l];
     if (L.kind == kSnDense && L.Co > kSnThreads && mode == 0) return -3;
     if (L.in < 0 || L.out < 0 || L.in >= kSnLds || L.out >= kSnLds) return -4;
+    if (L.drop_rate != 0) {
+      float rate;
+      memcpy(&rate, &L.drop_rate, sizeof(rate));
+      if (!(rate > 0.f && rate < 1.f) || l == nl - 1 || L.drop_n != L.Ho * L.Wo * L.Co || L.drop_n < 1 ||
+          L.out + L.drop_n > kSnLds || (mode == 0 && !step))
+        return -7;
+      drops = true;
+    }
   }
   if (a.L[nl - 1].kind != kSnDense) return -5;
   a.nl = nl;
@@ -1097,6 +1152,7 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
   a.rec = rec;
   a.metrics = metrics;
   a.iterations = iterations;
+  a.step = (drops && mode == 0) ? step : nullptr;
   a.scale = scale;
   a.probs = probs;
   a.probs_softmax = probs_softmax;
@@ -1114,11 +1170,13 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
 // ranges: nr x {part_lo, n, flat_off}; dense: nd x {In, Co, xo, go, w_off, b_off, blk0, nblk}.
 // Grid: block 0 metrics, then conv_nblk conv blocks, then the dense blocks.  apply = 0 stores the
 // gradients into g; apply = 1 applies the optimizer (kind, lr, mom, b1, b2, eps) to w / m / v.
+// step (optional): device word that block 0 sets to *iterations, the step index of the next step's masks.
 TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
                                const float* part, int npart, const float* rec, int nrec, float* w, float* g, float* m,
-                               float* v, const long long* iterations, float* metrics, int apply, int kind, float lr,
-                               float mom, float b1, float b2, float eps, hipStream_t stream) {
+                               float* v, const long long* iterations, long long* step, float* metrics, int apply,
+                               int kind, float lr, float mom, float b1, float b2, float eps, hipStream_t stream) {
   if (nr > 2 * kSnMaxLayers || nd > kSnMaxLayers || B <= 0) return -1;
+  if (step && !iterations) return -2;
   if (apply && (!iterations || (kind != kOptSGD && !m) || (kind == kOptAdam && !v))) return -2;
   if (!apply && !g) return -2;
   SnWgradArgs a{};
@@ -1145,6 +1203,7 @@ TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int 
   a.m = m;
   a.v = v;
   a.iterations = iterations;
+  a.step = step;
   a.metrics = metrics;
   a.h = OptHyper{kind, lr, mom, b1, b2, eps};
   smallnet_wgrad_kernel<<<nblk, 256, 0, stream>>>(a);

@@ -109,9 +109,9 @@ _HIP_PROTOS = {
     "tde_gather_rows_dev": (i32, [p, i64, i64, p, i64, p, p, p]),
     "tde_copy_pairs": (i32, [i32, p, p, p, p]),
     "tde_smallnet_limits": (i32, [p]),
-    "tde_smallnet_step": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, f32, p, i32,
+    "tde_smallnet_step": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p, i32,
                                 p, p]),
-    "tde_smallnet_wgrad": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, i32, i32, f32, f32,
+    "tde_smallnet_wgrad": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p, i32, i32, f32, f32,
                                  f32, f32, f32, p]),
     "tde_dgrad_phase_zero": (i32, [p, p, C.c_uint, p]),
     "tde_stem_unpack_wgrad": (i32, [p, p, p, p]),

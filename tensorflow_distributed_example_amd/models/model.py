@@ -108,7 +108,7 @@ class Model:
             self.optimizer.iterations = int(step)
         for prog in self._programs.values():
             for plan in prog.plans:
-                plan.iterations.fill_(int(step))
+                plan.set_iterations(int(step))
 
     def _weights_changed(self):
         """Propagate replica-0 values to every replica and refresh kernel caches."""

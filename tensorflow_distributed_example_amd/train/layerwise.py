@@ -35,6 +35,7 @@ from ..models import layers as L
 from ..ops import layer_ops as O
 from ..ops import layer_ops32 as O32
 from . import program as PG
+from .elementwise_ids import dropout_seed, elementwise_chains
 
 bf16 = torch.bfloat16
 
@@ -175,9 +176,6 @@ class LayerwisePlan(PG.ReplicaPlan):
         def single(t):
             return nodes[t.consumers[0]] if len(t.consumers) == 1 else None
 
-        def is_relu(layer):
-            return isinstance(layer, L.Activation) and layer.activation == "relu"
-
         fused = set()        # node indices absorbed into another stage
         deferred = {}        # Add node index -> BN stage emitted at that position
         stages = []
@@ -200,7 +198,7 @@ class LayerwisePlan(PG.ReplicaPlan):
         if not isinstance(self.loss, SparseCategoricalCrossentropy):
             raise Unsupported(f"loss {type(self.loss).__name__} has no fused HIP kernel")
 
-        lid = 0
+        chains = elementwise_chains(nodes)    # stage ids and absorbed [Add] [ReLU] [Dropout] nodes
         for i, (layer, ins, out) in enumerate(nodes):
             if i in fused:
                 continue
@@ -221,37 +219,30 @@ class LayerwisePlan(PG.ReplicaPlan):
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
-                st = _Elementwise(self, layer, tin, tout, lid)
-                lid += 1
+                ch = chains[i]
+                st = _Elementwise(self, layer, tin, tout, ch["lid"])
                 # absorb the chain that follows: [Add] [ReLU] [Dropout]
                 cur = tout
                 chain = [tout]
                 if isinstance(layer, L.BatchNormalization):
                     st.stats_from_gemm = i in bn_fed
-                    c = single(cur)
-                    if c is not None and isinstance(c[0], L.Add) and len(c[1]) == 2 and nodes.index(c) not in fused:
-                        k = nodes.index(c)
-                        other = [T[j] for j in c[1] if j != out]
-                        if len(other) == 1:
-                            st.res = other[0]
-                            fused.add(k)
-                            cur = T[c[2]]
-                            chain.append(cur)
-                            st.defer_to = k
-                if not isinstance(layer, L.Dropout) and not (isinstance(layer, L.Activation)):
-                    c = single(cur)
-                    if c is not None and is_relu(c[0]):
-                        st.relu = True
-                        fused.add(nodes.index(c))
-                        cur = T[c[2]]
+                    if ch["add"] is not None:
+                        k = ch["add"]
+                        st.res = [T[j] for j in nodes[k][1] if j != out][0]
+                        fused.add(k)
+                        cur = T[nodes[k][2]]
                         chain.append(cur)
-                if not isinstance(layer, L.Dropout):
-                    c = single(cur)
-                    if c is not None and isinstance(c[0], L.Dropout):
-                        st.set_dropout(c[0])
-                        fused.add(nodes.index(c))
-                        cur = T[c[2]]
-                        chain.append(cur)
+                        st.defer_to = k
+                if ch["relu"] is not None:
+                    st.relu = True
+                    fused.add(ch["relu"])
+                    cur = T[nodes[ch["relu"]][2]]
+                    chain.append(cur)
+                if ch["drop"] is not None:
+                    st.set_dropout(nodes[ch["drop"]][0])
+                    fused.add(ch["drop"])
+                    cur = T[nodes[ch["drop"]][2]]
+                    chain.append(cur)
                 st.out = cur
                 for t in chain[:-1]:
                     t.alias = cur
@@ -743,9 +734,7 @@ class _Elementwise(_Stage):
         return self._pnames
 
     def set_dropout(self, layer):
-        g = Kb.make_generator(7919 + self.lid)
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) if layer.seed is None else int(layer.seed)
-        self.drop = O.DropSpec(layer.rate, seed, self.plan.iterations, self.lid)
+        self.drop = O.DropSpec(layer.rate, dropout_seed(layer, self.lid), self.plan.iterations, self.lid)
 
     def alloc(self, B, dev):
         C = self.inp.C

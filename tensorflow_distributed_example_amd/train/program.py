@@ -57,6 +57,10 @@ class ReplicaPlan:
     def reset_metrics(self):
         self.metrics.zero_()
 
+    def set_iterations(self, step):
+        """Assign the device step counter from the host (checkpoint restore)."""
+        self.iterations.fill_(int(step))
+
     def train_step(self, x, y, B=None):
         raise NotImplementedError
 

@@ -4,7 +4,11 @@ Model families: BASELINE.json config 2 (MNIST LeNet-5, ``zoo.lenet5``) and confi
 (``tf2_mnist_distributed.py``'s plumbing model, ``zoo.mnist_mlp``); any Sequential chain of
 ``Conv2D(stride 1, same/valid, relu|linear) [MaxPooling2D(2)]`` stages, ``Flatten``/``Reshape``,
 ``Dense(relu|linear)`` layers and a ``Dense`` head (logits, or softmax fed to the probability form of
-``SparseCategoricalCrossentropy``) whose per-image activations fit in one workgroup's LDS.
+``SparseCategoricalCrossentropy``) whose per-image activations fit in one workgroup's LDS.  A
+``Dropout`` may follow a Conv2D stage without a pool, a MaxPooling2D or a non-head Dense (a Flatten /
+Reshape or a standalone ``Activation("relu")`` may sit in between): the kernel multiplies that
+activation, and in the backward the gradient that lands on it, by the Philox keep scale in LDS -- the
+layer-wise plan's mask, element for element (``train/elementwise_ids.py``), regenerated, never stored.
 
 A training step is two HIP launches (``csrc/kernels/smallnet.hip``): one workgroup per image runs the
 forward, the loss and the whole input-gradient chain out of LDS and leaves per-image conv weight
@@ -27,11 +31,13 @@ import torch
 from .. import _native as N
 from ..losses import SparseCategoricalCrossentropy
 from ..models import layers as L
+from .elementwise_ids import dropout_ids
 from .program import OptimizerKernel, ReplicaPlan
 
 CONV, POOL, DENSE = 0, 1, 2
 _FIELDS = ("kind", "relu", "mask_in", "need_gin", "H", "W", "C", "Ho", "Wo", "Co", "kh", "kw", "pt", "pl",
-           "w_off", "b_off", "in", "out", "wl", "part", "xo", "go")
+           "w_off", "b_off", "in", "out", "wl", "part", "xo", "go",
+           "drop_rate", "drop_seed_lo", "drop_seed_hi", "drop_lid", "drop_n")
 
 
 def _limits():
@@ -57,7 +63,8 @@ def _chain(model):
 
 
 def match_smallnet(model, loss):
-    """Per-layer description of a supported model, or None."""
+    """Per-layer description of a supported model, or None.  One entry per Conv2D / MaxPooling2D / Dense;
+    ``drop`` is the Dropout layer applied to the entry's output (after its ReLU), or None."""
     if not isinstance(loss, SparseCategoricalCrossentropy):
         return None
     chain = _chain(model)
@@ -82,7 +89,8 @@ def match_smallnet(model, loss):
                 return None
             continue
         if isinstance(layer, L.Activation):
-            if layer.activation != "relu" or not spec or spec[-1]["kind"] == POOL or spec[-1]["relu"]:
+            if (layer.activation != "relu" or not spec or spec[-1]["kind"] == POOL or spec[-1]["relu"]
+                    or spec[-1]["drop"] is not None):
                 return None
             spec[-1]["relu"] = 1
             continue
@@ -95,7 +103,7 @@ def match_smallnet(model, loss):
             if Ho < 1 or Wo < 1:
                 return None
             spec.append(dict(kind=CONV, layer=layer, inp=(H, W, C), outp=(Ho, Wo, Co),
-                             relu=int(layer.activation == "relu"), pt=pt, pl=pl, pb=pb, pr=pr))
+                             relu=int(layer.activation == "relu"), pt=pt, pl=pl, pb=pb, pr=pr, drop=None))
             shape = (Ho, Wo, Co)
             continue
         if isinstance(layer, L.MaxPooling2D):
@@ -104,21 +112,29 @@ def match_smallnet(model, loss):
             H, W, C = shape
             if H < 2 or W < 2 or not spec or spec[-1]["kind"] != CONV:
                 return None
-            spec.append(dict(kind=POOL, layer=layer, inp=shape, outp=(H // 2, W // 2, C), relu=0))
+            if spec[-1]["drop"] is not None:   # the pool backward recomputes the argmax from the conv output
+                return None
+            spec.append(dict(kind=POOL, layer=layer, inp=shape, outp=(H // 2, W // 2, C), relu=0, drop=None))
             shape = (H // 2, W // 2, C)
             continue
         if isinstance(layer, L.Dense):
             if shape[0] != 1 or shape[1] != 1 or layer.activation not in (None, "linear", "relu", "softmax"):
                 return None
             spec.append(dict(kind=DENSE, layer=layer, inp=shape, outp=(1, 1, layer.units),
-                             relu=int(layer.activation == "relu")))
+                             relu=int(layer.activation == "relu"), drop=None))
             shape = (1, 1, layer.units)
             continue
-        return None       # Dropout, BatchNormalization, strided conv, ...: other plans
+        if isinstance(layer, L.Dropout):
+            # on the output of the last entry; not on the raw input, not twice on one activation
+            if not spec or spec[-1]["drop"] is not None or not 0.0 <= layer.rate < 1.0:
+                return None
+            spec[-1]["drop"] = layer
+            continue
+        return None       # BatchNormalization, strided conv, other poolings, ...: other plans
     if not spec or spec[-1]["kind"] != DENSE:
         return None
     head = spec[-1]["layer"]
-    if head.activation == "relu" or spec[-1]["relu"]:
+    if head.activation == "relu" or spec[-1]["relu"] or spec[-1]["drop"] is not None:
         return None
     if (head.activation == "softmax") == bool(loss.from_logits):
         return None
@@ -162,6 +178,8 @@ class SmallNetPlan(ReplicaPlan):
         ranges = []
         dense = []
         prev_out, prev_kind, prev_relu = self.in0, None, 0
+        ids = dropout_ids(model) if any(s["drop"] is not None for s in spec) else {}
+        self.drops = []       # (entry index, rate, seed, lid, D) of every Dropout with rate > 0
         for i, s in enumerate(spec):
             lay = s["layer"]
             H, W, C = s["inp"]
@@ -194,6 +212,13 @@ class SmallNetPlan(ReplicaPlan):
                 dense.append([In, Co, rec, rec + In, r["w_off"], r["b_off"], 0, -(-In // 16) * -(-(-(-Co // 16)) // 4)])
                 rec += In + Co
             r["out"] = off
+            if s["drop"] is not None and s["drop"].rate > 0:      # rate 0 is the identity: no fields, no pass
+                lid, seed = ids[s["drop"].name]
+                rate = np.float32(s["drop"].rate)
+                lo, hi = (np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32))
+                r.update(drop_rate=int(rate.view(np.int32)), drop_seed_lo=int(lo), drop_seed_hi=int(hi), drop_lid=lid,
+                         drop_n=Ho * Wo * Co)
+                self.drops.append((i, float(rate), seed & (2 ** 64 - 1), lid, Ho * Wo * Co))
             off = _a4(off + Ho * Wo * Co)
             rows.append([r[f] for f in _FIELDS])
             prev_out, prev_kind, prev_relu = r["out"], s["kind"], s["relu"]
@@ -220,6 +245,10 @@ class SmallNetPlan(ReplicaPlan):
         self.rec = torch.zeros(B, self.nrec, dtype=torch.float32, device=dev)
         self.probs = torch.zeros(B, self.ncls, dtype=torch.float32, device=dev)
         self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
+        # the step index of the dropout masks: steps completed before the running one.  The step kernel
+        # increments ``iterations`` while its grid runs, so it reads this word instead, which the weight
+        # gradient launch sets to ``iterations`` for the next step.
+        self.step_word = self.iterations.clone() if self.drops else None
         self.stamps = None       # int64[64] to record workgroup 0's phase clock (bench/smallnet_phases.py)
 
     # ------------------------------------------------------------------ step modes
@@ -231,6 +260,11 @@ class SmallNetPlan(ReplicaPlan):
     def xg_apply_spec(self):
         from .program import f32_xg_apply_spec
         return f32_xg_apply_spec(self)
+
+    def set_iterations(self, step):
+        super().set_iterations(step)
+        if self.step_word is not None:
+            self.step_word.fill_(int(step))
 
     def _step(self, mode, x, y, B, probs=None):
         if B > self.B:
@@ -247,7 +281,7 @@ class SmallNetPlan(ReplicaPlan):
             self.x_stride, self.in0, self.n_in0, self.img.ctypes.data, N.ptr(y),
             self.part.data_ptr() if train else None, self.npart,
             self.rec.data_ptr() if train else None, self.nrec, self.metrics.data_ptr(),
-            self.iterations.data_ptr(), float(self.scale), N.ptr(probs), self.probs_softmax, N.ptr(self.stamps),
+            self.iterations.data_ptr(), N.ptr(self.step_word), float(self.scale), N.ptr(probs), self.probs_softmax, N.ptr(self.stamps),
             N.stream_ptr())
         N.check(rc, "tde_smallnet_step")
 
@@ -266,7 +300,8 @@ class SmallNetPlan(ReplicaPlan):
         rc = self.lib.tde_smallnet_wgrad(
             self.ranges.ctypes.data, self.nranges, self.dense.ctypes.data, len(self.dense), self.conv_nblk, B,
             self.part.data_ptr(), self.npart, self.rec.data_ptr(), self.nrec, st.w.data_ptr(), st.g.data_ptr(),
-            N.ptr(m), N.ptr(v), self.iterations.data_ptr(), self.metrics.data_ptr(), int(local), kind, lr,
+            N.ptr(m), N.ptr(v), self.iterations.data_ptr(), N.ptr(self.step_word), self.metrics.data_ptr(), int(local),
+            kind, lr,
             hp["mom"], hp["b1"], hp["b2"], hp["eps"], N.stream_ptr())
         N.check(rc, "tde_smallnet_wgrad")
 
