@@ -24,9 +24,9 @@ for name in sys.argv[1:] or ["lenet5", "mnist_mlp"]:
         plan.train_step(x, y)
     torch.cuda.synchronize()
     st = plan.stamps.cpu().numpy()
-    labels = ["start"] + [f"fwd{i}:{'CPD'[k]}" for i, k in enumerate(plan.layers[:, 0])] + ["loss"]
+    labels = ["start"] + [f"fwd{i}:{'CPDA'[k]}" for i, k in enumerate(plan.layers[:, 0])] + ["loss"]
     for i, k in reversed(list(enumerate(plan.layers[:, 0]))):
-        labels += [f"bwd{i}:wgrad", f"bwd{i}:dgrad"] if k == 0 else [f"bwd{i}:{'CPD'[k]}"]
+        labels += [f"bwd{i}:wgrad", f"bwd{i}:dgrad"] if k == 0 else [f"bwd{i}:{'CPDA'[k]}"]
     n = len(labels)
     us = (st[:n] - st[0]) / 100.0     # 100 MHz wall clock -> us
     print(json.dumps({"model": name, "phase_end_us": {l: round(float(u), 2) for l, u in zip(labels, us)}}))

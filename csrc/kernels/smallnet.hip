@@ -1,6 +1,7 @@
 // Fused training step for small image classifiers whose trunk is per-image: LeNet-5
 // (BASELINE.json config 2), dense MLPs (tf2_mnist_distributed.py's CPU plumbing config) and any
-// [Conv2D(stride 1, relu) [MaxPooling2D(2)]]* Flatten Dense* head with sparse softmax-CE.
+// [Conv2D(stride 1, act) [MaxPooling2D(2) | AveragePooling2D(2)]]* Flatten Dense(act)* head with sparse
+// softmax-CE, act = linear / relu / tanh / sigmoid (LeCun's tanh / average-pool LeNet-5 included).
 //
 // MI355X-first design: at MNIST sizes a whole image's activations (LeNet-5: 8.9K floats) fit in LDS, so
 // one workgroup owns one image and runs the forward, the loss and the whole input-gradient chain out
@@ -9,8 +10,9 @@
 //
 //   smallnet_step_kernel   grid = batch.  Forward (conv / pool / dense, fp32 FMA), softmax-CE with
 //                          (p - onehot) / global_batch into the logits buffer, then the backward in
-//                          place (every gradient overwrites the activation it belongs to, masked by
-//                          that activation's ReLU), per-image conv weight/bias gradients into `part`,
+//                          place (every gradient overwrites the activation it belongs to, times that
+//                          activation's derivative, which is a function of the value being overwritten:
+//                          y > 0, 1 - y^2, y (1 - y)), per-image conv weight/bias gradients into `part`,
 //                          dense inputs and pre-activation gradients into `rec`.  A Dropout layer is a
 //                          multiply of its owner's output in LDS by the Philox keep scale (forward) and of
 //                          the gradient that lands on that buffer by the regenerated scale (backward).
@@ -36,13 +38,15 @@ namespace tde {
 constexpr int kSnMaxLayers = 12;
 constexpr int kSnLds = 28 * 1024;  // floats of LDS per workgroup (112 KiB)
 constexpr int kSnThreads = 512;
-enum { kSnConv = 0, kSnPool = 1, kSnDense = 2 };
+enum { kSnConv = 0, kSnPool = 1, kSnDense = 2, kSnAvgPool = 3 };
+enum { kSnLinear = 0, kSnRelu = 1, kSnTanh = 2, kSnSigmoid = 3 };  // activation codes
 
 // All offsets in floats.  Buffers: `in` / `out` are the layer's input / output activations in LDS;
-// after the consumer's backward `out` holds the gradient w.r.t. this layer's output (masked by its
-// ReLU), and this layer's backward writes its input gradient into `in` (masked when mask_in).
+// after the consumer's backward `out` holds the gradient w.r.t. this layer's pre-activation, and this
+// layer's backward writes its input gradient into `in`, times the derivative of the activation that
+// produced `in` (code mask_in; for a pool: the activation of the conv in front of it).
 struct SnLayer {
-  int kind, relu, mask_in, need_gin;
+  int kind, act, mask_in, need_gin;
   int H, W, C, Ho, Wo, Co;
   int kh, kw, pt, pl;
   int w_off, b_off;    // flat weight offsets (b_off < 0: no bias)
@@ -72,8 +76,43 @@ struct SnArgs {
   float* probs;
   int probs_softmax;
   long long* stamps;  // optional phase timestamps of workgroup 0 (wall clock, 100 MHz)
+  int nonlinear;      // a layer has a tanh / sigmoid code or is an average pool: run sn_step<true>
   int mfma;           // phases (bit 0 fwd, 1 wgrad, 2 dgrad) of the compile-time-geometry convs on the f32 MFMA
 };
+
+// The step kernel holds its per-image program twice (sn_step<NL>, chosen per launch): NL = false knows
+// linear and relu only, the same source as when `act` was a relu flag (with one program LeNet-5 and the MLP
+// measured 1 - 3 % slower with tanhf / expf code in their conv and dense epilogues, none of it executed;
+// with this split they measure no slower than before -- the generated code was timed, not compared);
+// NL = true also knows tanh, sigmoid and the average pool.  Every phase is
+// __forceinline__: with two programs in one kernel the inliner otherwise leaves calls, and a by-value
+// SnLayer on the stack.
+//
+// Activation by code over the N pre-activations a thread holds.  tanhf / expf are the accurate library
+// forms; sigmoid of a large negative z is 1 / inf = 0.
+template <bool NL, int N>
+__device__ __forceinline__ void sn_act(int code, float* v) {
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    if (NL ? code == kSnRelu : code != 0) v[k] = fmaxf(v[k], 0.f);
+  if constexpr (NL) {
+    if (code > kSnRelu) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) v[k] = code == kSnTanh ? tanhf(v[k]) : 1.f / (1.f + expf(-v[k]));
+    }
+  }
+}
+
+// Gradient g through the activation with code != 0 and output y (the value the caller is about to
+// overwrite)
+template <bool NL>
+__device__ __forceinline__ float sn_act_bwd(int code, float y, float g) {
+  if constexpr (NL) {
+    if (code == kSnTanh) return g * fmaf(-y, y, 1.f);
+    if (code == kSnSigmoid) return g * (y * (1.f - y));
+  }
+  return y > 0.f ? g : 0.f;
+}
 
 template <int CG>
 __device__ __forceinline__ void ld_cg(const float* p, float* v) {
@@ -109,8 +148,8 @@ constexpr int kSnItemsTarget = 1024;
 
 // conv forward: item = (output pixel p, channel group g); pixels fastest, so a wave shares g and its
 // kernel reads are LDS broadcasts
-template <int CG>
-__device__ void sn_conv_fwd(const SnLayer L, float* s) {
+template <bool NL, int CG>
+__device__ __forceinline__ void sn_conv_fwd(const SnLayer L, float* s) {
   const float* in = s + L.in;
   const float* wl = s + L.wl;
   float* out = s + L.out;
@@ -159,10 +198,8 @@ __device__ void sn_conv_fwd(const SnLayer L, float* s) {
       }
     }
 #pragma unroll
-    for (int k = 0; k < CG; ++k) {
-      acc[k] += acc2[k];
-      if (L.relu) acc[k] = fmaxf(acc[k], 0.f);
-    }
+    for (int k = 0; k < CG; ++k) acc[k] += acc2[k];
+    sn_act<NL, CG>(L.act, acc);
     st_cg<CG>(out + p * L.Co + g * CG, acc);
   }
 }
@@ -171,7 +208,7 @@ __device__ void sn_conv_fwd(const SnLayer L, float* s) {
 // t fastest (the output-gradient reads are broadcasts).  With more than one slice the partials meet in
 // LDS scratch (float atomics); the bias sums ride along as t = T.
 template <int CG>
-__device__ void sn_conv_wgrad(const SnLayer L, float* s, float* part) {
+__device__ __forceinline__ void sn_conv_wgrad(const SnLayer L, float* s, float* part) {
   const float* in = s + L.in;
   const float* dz = s + L.out;
   const int T = L.kh * L.kw * L.C, ng = L.Co / CG;
@@ -248,8 +285,8 @@ __device__ void sn_conv_wgrad(const SnLayer L, float* s, float* part) {
 
 // conv input gradient, written over the input activation: item = (input pixel q, channel ci), q
 // fastest (the kernel reads are broadcasts)
-template <int CG>
-__device__ void sn_conv_dgrad(const SnLayer L, float* s) {
+template <bool NL, int CG>
+__device__ __forceinline__ void sn_conv_dgrad(const SnLayer L, float* s) {
   float* in = s + L.in;
   const float* dz = s + L.out;
   const float* wl = s + L.wl;
@@ -295,7 +332,7 @@ __device__ void sn_conv_dgrad(const SnLayer L, float* s) {
     }
     acc += acc2;
     const int e = q * L.C + ci;
-    if (L.mask_in && !(in[e] > 0.f)) acc = 0.f;
+    if (L.mask_in) acc = sn_act_bwd<NL>(L.mask_in, in[e], acc);
     in[e] = acc;
   }
 }
@@ -312,8 +349,8 @@ constexpr int sn_slices(int Ho, int items) {
   return best;
 }
 
-template <int CG, int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
-__device__ void sn_conv_fwd_c(const SnLayer L, float* s) {
+template <bool NL, int CG, int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
+__device__ __forceinline__ void sn_conv_fwd_c(const SnLayer L, float* s) {
   constexpr int P = Ho * Wo, NG = Co / CG;
   const float* in = s + L.in;
   const float* wl = s + L.wl;
@@ -349,14 +386,27 @@ __device__ void sn_conv_fwd_c(const SnLayer L, float* s) {
 #pragma unroll
     for (int k = 0; k < CG; ++k) {
       acc[k] += acc2[k];
-      if (L.relu) acc[k] = fmaxf(acc[k], 0.f);
+      if (NL ? L.act == kSnRelu : L.act != 0) acc[k] = fmaxf(acc[k], 0.f);
     }
     st_cg<CG>(out + p * Co + g * CG, acc);
+  }
+  // tanh / sigmoid in a loop of their own, every thread over the values it has just stored (no barrier):
+  // any form of them in the epilogue above took the step kernel past 256 VGPRs into scratch
+  if constexpr (NL) {
+    if (L.act > kSnRelu) {
+      for (int it = threadIdx.x; it < P * NG; it += kSnThreads) {
+        float* o = out + (it % P) * Co + (it / P) * CG;
+        float v[CG];
+        ld_cg<CG>(o, v);
+        sn_act<NL, CG>(L.act, v);
+        st_cg<CG>(o, v);
+      }
+    }
   }
 }
 
 template <int CG, int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
-__device__ void sn_conv_wgrad_c(const SnLayer L, float* s, float* part) {
+__device__ __forceinline__ void sn_conv_wgrad_c(const SnLayer L, float* s, float* part) {
   constexpr int T = KH * KW * C, NG = Co / CG;
   constexpr int S = sn_slices(Ho, T * NG), R = Ho / S;
   static_assert(T * Co + Co <= kSnScratch, "scratch");
@@ -414,8 +464,8 @@ __device__ void sn_conv_wgrad_c(const SnLayer L, float* s, float* part) {
   for (int i = threadIdx.x; i < nw; i += kSnThreads) part[L.part + i] = red[i];
 }
 
-template <int CG, int KH, int KW, int C, int Co, int Win, int Hin, int Ho, int Wo>
-__device__ void sn_conv_dgrad_c(const SnLayer L, float* s) {
+template <bool NL, int CG, int KH, int KW, int C, int Co, int Win, int Hin, int Ho, int Wo>
+__device__ __forceinline__ void sn_conv_dgrad_c(const SnLayer L, float* s) {
   constexpr int Q = Hin * Win;
   float* in = s + L.in;
   const float* dz = s + L.out;
@@ -449,7 +499,7 @@ __device__ void sn_conv_dgrad_c(const SnLayer L, float* s) {
     }
     acc += acc2;
     const int e = q * C + ci;
-    if (L.mask_in && !(in[e] > 0.f)) acc = 0.f;
+    if (L.mask_in) acc = sn_act_bwd<NL>(L.mask_in, in[e], acc);
     in[e] = acc;
   }
 }
@@ -475,8 +525,8 @@ __device__ __forceinline__ f32x4 sn_mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
-__device__ void sn_conv_fwd_m(const SnLayer L, float* s) {
+template <bool NL, int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
+__device__ __forceinline__ void sn_conv_fwd_m(const SnLayer L, float* s) {
   constexpr int P = Ho * Wo, K = KH * KW * C, KS = (K + 3) / 4, MT = (P + 15) / 16, NT = (Co + 15) / 16;
   const float* in = s + L.in;
   const float* wl = s + L.wl;
@@ -503,7 +553,7 @@ __device__ void sn_conv_fwd_m(const SnLayer L, float* s) {
       for (int i = 0; i < 4; ++i) {
         const int pr = mt * 16 + 4 * fq + i;
         float v = acc[i] + bias;
-        if (L.relu) v = fmaxf(v, 0.f);
+        sn_act<NL, 1>(L.act, &v);
         if (pr < P) out[pr * Co + co] = v;
       }
     }
@@ -511,7 +561,7 @@ __device__ void sn_conv_fwd_m(const SnLayer L, float* s) {
 }
 
 template <int KH, int KW, int C, int Co, int Win, int Ho, int Wo>
-__device__ void sn_conv_wgrad_m(const SnLayer L, float* s, float* part) {
+__device__ __forceinline__ void sn_conv_wgrad_m(const SnLayer L, float* s, float* part) {
   constexpr int T = KH * KW * C, T1 = T + 1, P = Ho * Wo, PS = (P + 3) / 4;
   constexpr int MT = (T1 + 15) / 16, NT = (Co + 15) / 16;
   constexpr int S0 = kSnWaves / (MT * NT) > 0 ? kSnWaves / (MT * NT) : 1;
@@ -557,8 +607,8 @@ __device__ void sn_conv_wgrad_m(const SnLayer L, float* s, float* part) {
   }
 }
 
-template <int KH, int KW, int C, int Co, int Win, int Hin, int Ho, int Wo>
-__device__ void sn_conv_dgrad_m(const SnLayer L, float* s) {
+template <bool NL, int KH, int KW, int C, int Co, int Win, int Hin, int Ho, int Wo>
+__device__ __forceinline__ void sn_conv_dgrad_m(const SnLayer L, float* s) {
   // two M tiles per item share every B fragment (the weights depend only on k and ci): half the weight
   // reads per MFMA and two independent accumulator chains per wave
   constexpr int Q = Hin * Win, K = KH * KW * Co, KS = (K + 3) / 4, MT = (Q + 15) / 16, NT = (C + 15) / 16;
@@ -600,7 +650,7 @@ __device__ void sn_conv_dgrad_m(const SnLayer L, float* s) {
           if (qr < Q) {
             const int e = qr * C + ci;
             float v = acc[h][i];
-            if (L.mask_in && !(in[e] > 0.f)) v = 0.f;
+            if (L.mask_in) v = sn_act_bwd<NL>(L.mask_in, in[e], v);
             in[e] = v;
           }
         }
@@ -616,6 +666,7 @@ __device__ void sn_conv_dgrad_m(const SnLayer L, float* s) {
   X(3, 3, 1, 32, 28, 28)
 
 // phase 0 forward, 1 weight gradient, 2 input gradient; false when the geometry is not compiled in
+template <bool NL>
 __device__ __forceinline__ bool sn_conv_fast(int phase, const SnLayer L, float* s, float* part, int mfma) {
   if (L.pt != 0 || L.pl != 0) return false;
 #define SN_FAST_CASE(KH_, KW_, C_, CO_, H_, W_)                                                              \
@@ -623,14 +674,14 @@ __device__ __forceinline__ bool sn_conv_fast(int phase, const SnLayer L, float* 
     constexpr int CG = (CO_ % 4 == 0) ? 4 : ((CO_ % 2 == 0) ? 2 : 1);                                        \
     constexpr int HO = H_ - KH_ + 1, WO = W_ - KW_ + 1;                                                      \
     if (mfma & (1 << phase)) {                                                                               \
-      if (phase == 0) sn_conv_fwd_m<KH_, KW_, C_, CO_, W_, HO, WO>(L, s);                                    \
+      if (phase == 0) sn_conv_fwd_m<NL, KH_, KW_, C_, CO_, W_, HO, WO>(L, s);                                    \
       else if (phase == 1) sn_conv_wgrad_m<KH_, KW_, C_, CO_, W_, HO, WO>(L, s, part);                       \
-      else sn_conv_dgrad_m<KH_, KW_, C_, CO_, W_, H_, HO, WO>(L, s);                                         \
+      else sn_conv_dgrad_m<NL, KH_, KW_, C_, CO_, W_, H_, HO, WO>(L, s);                                         \
       return true;                                                                                           \
     }                                                                                                        \
-    if (phase == 0) sn_conv_fwd_c<CG, KH_, KW_, C_, CO_, W_, HO, WO>(L, s);                                  \
+    if (phase == 0) sn_conv_fwd_c<NL, CG, KH_, KW_, C_, CO_, W_, HO, WO>(L, s);                                  \
     else if (phase == 1) sn_conv_wgrad_c<CG, KH_, KW_, C_, CO_, W_, HO, WO>(L, s, part);                     \
-    else sn_conv_dgrad_c<CG, KH_, KW_, C_, CO_, W_, H_, HO, WO>(L, s);                                       \
+    else sn_conv_dgrad_c<NL, CG, KH_, KW_, C_, CO_, W_, H_, HO, WO>(L, s);                                       \
     return true;                                                                                             \
   }
   SN_FAST_GEOS(SN_FAST_CASE)
@@ -639,7 +690,7 @@ __device__ __forceinline__ bool sn_conv_fast(int phase, const SnLayer L, float* 
 }
 
 // ---------------------------------------------------------------------------------------
-__device__ void sn_pool_fwd(const SnLayer L, float* s) {
+__device__ __forceinline__ void sn_pool_fwd(const SnLayer L, float* s) {
   const float* in = s + L.in;
   float* out = s + L.out;
   const int n = L.Ho * L.Wo * L.C;
@@ -650,8 +701,10 @@ __device__ void sn_pool_fwd(const SnLayer L, float* s) {
   }
 }
 
-// gradient routed to the first maximum of each window (scan order), written over the window
-__device__ void sn_pool_bwd(const SnLayer L, float* s) {
+// gradient routed to the first maximum of each window (scan order), times the conv activation's
+// derivative there, written over the window
+template <bool NL>
+__device__ __forceinline__ void sn_pool_bwd(const SnLayer L, float* s) {
   float* in = s + L.in;
   const float* g = s + L.out;
   const int n = L.Ho * L.Wo * L.C;
@@ -666,9 +719,45 @@ __device__ void sn_pool_bwd(const SnLayer L, float* s) {
 #pragma unroll
     for (int k = 1; k < 4; ++k)
       if (v[k] > v[am]) am = k;
-    const float gv = (L.mask_in && !(v[am] > 0.f)) ? 0.f : g[it];
+    const float gv = L.mask_in ? sn_act_bwd<NL>(L.mask_in, v[am], g[it]) : g[it];
 #pragma unroll
     for (int k = 0; k < 4; ++k) p[o[k]] = k == am ? gv : 0.f;
+  }
+  if (L.H != 2 * L.Ho || L.W != 2 * L.Wo) {  // odd edge rows / columns feed no window
+    for (int it = threadIdx.x; it < L.H * L.W * L.C; it += kSnThreads) {
+      const int hw = it / L.C, h = hw / L.W, w = hw - h * L.W;
+      if (h >= 2 * L.Ho || w >= 2 * L.Wo) in[it] = 0.f;
+    }
+  }
+}
+
+// 2x2 average pool; a thread per (window, channel), channels fastest like sn_pool_fwd, so a wave's four
+// reads and its write each cover consecutive LDS words
+__device__ __forceinline__ void sn_avgpool_fwd(const SnLayer L, float* s) {
+  const float* in = s + L.in;
+  float* out = s + L.out;
+  const int n = L.Ho * L.Wo * L.C;
+  for (int it = threadIdx.x; it < n; it += kSnThreads) {
+    const int c = it % L.C, pw = (it / L.C) % L.Wo, ph = it / (L.C * L.Wo);
+    const float* p = in + ((2 * ph) * L.W + 2 * pw) * L.C + c;
+    out[it] = 0.25f * ((p[0] + p[L.C]) + (p[L.W * L.C] + p[L.W * L.C + L.C]));
+  }
+}
+
+// a quarter of the window's gradient to each of its four elements, times the conv activation's
+// derivative at that element, written over the window
+template <bool NL>
+__device__ __forceinline__ void sn_avgpool_bwd(const SnLayer L, float* s) {
+  float* in = s + L.in;
+  const float* g = s + L.out;
+  const int n = L.Ho * L.Wo * L.C;
+  for (int it = threadIdx.x; it < n; it += kSnThreads) {
+    const int c = it % L.C, pw = (it / L.C) % L.Wo, ph = it / (L.C * L.Wo);
+    float* p = in + ((2 * ph) * L.W + 2 * pw) * L.C + c;
+    const int o[4] = {0, L.C, L.W * L.C, L.W * L.C + L.C};
+    const float gv = 0.25f * g[it];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[o[k]] = L.mask_in ? sn_act_bwd<NL>(L.mask_in, p[o[k]], gv) : gv;
   }
   if (L.H != 2 * L.Ho || L.W != 2 * L.Wo) {  // odd edge rows / columns feed no window
     for (int it = threadIdx.x; it < L.H * L.W * L.C; it += kSnThreads) {
@@ -683,7 +772,8 @@ __device__ void sn_pool_bwd(const SnLayer L, float* s) {
 // flight, not FLOPs: a thread owns 4 adjacent outputs (one float4 of a W row) and a slice of the inputs,
 // 16 independent row loads are issued before their FMAs, and the S slices are summed through LDS.
 
-__device__ void sn_dense_fwd(const SnLayer L, float* s, const float* w, float* scratch, float* rec, bool train) {
+template <bool NL>
+__device__ __forceinline__ void sn_dense_fwd(const SnLayer L, float* s, const float* w, float* scratch, float* rec, bool train) {
   const float* in = s + L.in;
   float* out = s + L.out;
   const int In = L.C, Co = L.Co, T = kSnThreads;
@@ -741,13 +831,15 @@ __device__ void sn_dense_fwd(const SnLayer L, float* s, const float* w, float* s
   for (int j = threadIdx.x; j < Co; j += T) {
     float acc = L.b_off >= 0 ? w[L.b_off + j] : 0.f;
     for (int k = 0; k < S; ++k) acc += scratch[k * Co + j];
-    out[j] = L.relu ? fmaxf(acc, 0.f) : acc;
+    sn_act<NL, 1>(L.act, &acc);
+    out[j] = acc;
   }
 }
 
 // dense backward: the pre-activation gradient (in `out`) to `rec`, the input gradient over `in`
 // (a thread per input row; the row's float4s are issued together)
-__device__ void sn_dense_bwd(const SnLayer L, float* s, const float* w, float* rec) {
+template <bool NL>
+__device__ __forceinline__ void sn_dense_bwd(const SnLayer L, float* s, const float* w, float* rec) {
   float* in = s + L.in;
   const float* dz = s + L.out;
   const int In = L.C, Co = L.Co;
@@ -791,7 +883,7 @@ __device__ void sn_dense_bwd(const SnLayer L, float* s, const float* w, float* r
     } else {
       for (int j = 0; j < Co; ++j) acc = fmaf(wr[j], dz[j], acc);
     }
-    if (L.mask_in && !(in[i] > 0.f)) acc = 0.f;
+    if (L.mask_in) acc = sn_act_bwd<NL>(L.mask_in, in[i], acc);
     in[i] = acc;
   }
 }
@@ -800,7 +892,7 @@ __device__ void sn_dense_bwd(const SnLayer L, float* s, const float* w, float* r
 // place: row b of the [B, D] activation is elements b D .. b D + D - 1 of the layer's Philox stream, one
 // block per 4 consecutive elements -- b D need not be a multiple of 4, so the first and the last block
 // of a row straddle it and their words outside the row are dropped.
-__device__ void sn_drop(const SnLayer L, float* s, long long step, int b) {
+__device__ __forceinline__ void sn_drop(const SnLayer L, float* s, long long step, int b) {
   float* v = s + L.out;
   const float rate = __int_as_float(L.drop_rate);
   const unsigned long long seed = (unsigned)L.drop_seed_lo | ((unsigned long long)(unsigned)L.drop_seed_hi << 32);
@@ -823,8 +915,8 @@ __device__ __forceinline__ void sn_by_cg(int Co, F&& f) {
   else f(std::integral_constant<int, 1>{});
 }
 
-__global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
-  __shared__ __attribute__((aligned(16))) float s[kSnLds];
+template <bool NL>
+__device__ __forceinline__ void sn_step(const SnArgs& a, float* s) {
   const int b = blockIdx.x;
   const bool train = a.mode == 0;
   float* scratch = s;  // [kSnScratch] dense slice partials
@@ -863,11 +955,14 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
   for (int l = 0; l < a.nl; ++l) {
     const SnLayer L = a.L[l];
     if (L.kind == kSnConv) {
-      if (!sn_conv_fast(0, L, s, nullptr, a.mfma)) sn_by_cg(L.Co, [&](auto cg) { sn_conv_fwd<decltype(cg)::value>(L, s); });
+      if (!sn_conv_fast<NL>(0, L, s, nullptr, a.mfma))
+        sn_by_cg(L.Co, [&](auto cg) { sn_conv_fwd<NL, decltype(cg)::value>(L, s); });
     } else if (L.kind == kSnPool) {
       sn_pool_fwd(L, s);
+    } else if (NL && L.kind == kSnAvgPool) {
+      sn_avgpool_fwd(L, s);
     } else {
-      sn_dense_fwd(L, s, a.w, scratch, rec, train);
+      sn_dense_fwd<NL>(L, s, a.w, scratch, rec, train);
     }
     __syncthreads();
     if (train && L.drop_rate != 0) {  // before any consumer reads it (a Dense consumer records it for the wgrad)
@@ -936,20 +1031,28 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
       __syncthreads();
     }
     if (L.kind == kSnConv) {
-      if (!sn_conv_fast(1, L, s, part, a.mfma))
+      if (!sn_conv_fast<NL>(1, L, s, part, a.mfma))
         sn_by_cg(L.Co, [&](auto cg) { sn_conv_wgrad<decltype(cg)::value>(L, s, part); });
       __syncthreads();  // the weight gradient reads the input the input gradient overwrites
       stamp();
-      if (L.need_gin && !sn_conv_fast(2, L, s, nullptr, a.mfma))
-        sn_by_cg(L.Co, [&](auto cg) { sn_conv_dgrad<decltype(cg)::value>(L, s); });
+      if (L.need_gin && !sn_conv_fast<NL>(2, L, s, nullptr, a.mfma))
+        sn_by_cg(L.Co, [&](auto cg) { sn_conv_dgrad<NL, decltype(cg)::value>(L, s); });
     } else if (L.kind == kSnPool) {
-      sn_pool_bwd(L, s);
+      sn_pool_bwd<NL>(L, s);
+    } else if (NL && L.kind == kSnAvgPool) {
+      sn_avgpool_bwd<NL>(L, s);
     } else {
-      sn_dense_bwd(L, s, a.w, rec);
+      sn_dense_bwd<NL>(L, s, a.w, rec);
     }
     __syncthreads();
     stamp();
   }
+}
+
+__global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
+  __shared__ __attribute__((aligned(16))) float s[kSnLds];
+  if (a.nonlinear) sn_step<true>(a, s);
+  else sn_step<false>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1098,7 +1201,8 @@ TDE_API int tde_smallnet_limits(int* out) {
   return 0;
 }
 
-// layers: nl x kSnLayerInts int32 (SnLayer field order).  mode 0 train (part / rec written,
+// layers: nl x kSnLayerInts int32 (SnLayer field order; kind: 0 conv, 1 max pool, 2 dense, 3 average pool;
+// act / mask_in: 0 linear, 1 relu, 2 tanh, 3 sigmoid; anything else returns -8).  mode 0 train (part / rec written,
 // iterations += 1), 1 eval (metrics += loss, correct, count), 2 predict (probs).  step: device word
 // holding the number of completed training steps, required when a layer drops (Dropout is the identity
 // in modes 1 and 2).
@@ -1116,6 +1220,10 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
     int* f = reinterpret_cast<int*>(&a.L[l]);
     for (int k = 0; k < kSnLayerInts; ++k) f[k] = layers[l * kSnLayerInts + k];
     const SnLayer L = a.L[l];
+    if (L.kind < kSnConv || L.kind > kSnAvgPool || L.act < kSnLinear || L.act > kSnSigmoid || L.mask_in < kSnLinear ||
+        L.mask_in > kSnSigmoid)
+      return -8;
+    if (L.act > kSnRelu || L.mask_in > kSnRelu || L.kind == kSnAvgPool) a.nonlinear = 1;
     if (L.kind == kSnDense && L.Co > kSnThreads && mode == 0) return -3;
     if (L.in < 0 || L.out < 0 || L.in >= kSnLds || L.out >= kSnLds) return -4;
     if (L.drop_rate != 0) {

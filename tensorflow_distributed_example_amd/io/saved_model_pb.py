@@ -7,8 +7,8 @@ tensor.proto, tensor_shape.proto, versions.proto).
 One MetaGraphDef tagged ``serve``:
 * GraphDef — the inference graph with TensorFlow's standard ops: ``Placeholder`` for the serving input,
   resource variables (``VarHandleOp`` + ``ReadVariableOp``, shared names = the TF1 variable names of the
-  exported TensorBundle), ``Reshape`` / ``Conv2D`` / ``BiasAdd`` / ``Relu`` / ``MaxPool`` /
-  ``FusedBatchNormV3`` (4-D, ``is_training=false``) or the Keras 2-D batchnorm arithmetic / ``MatMul`` /
+  exported TensorBundle), ``Reshape`` / ``Conv2D`` / ``BiasAdd`` / ``Relu`` / ``Tanh`` / ``Sigmoid`` /
+  ``MaxPool`` / ``AvgPool`` / ``FusedBatchNormV3`` (4-D, ``is_training=false``) or the Keras 2-D batchnorm arithmetic / ``MatMul`` /
   ``Softmax`` / ``AddV2`` / ``Mean`` / ``Pad`` / ``Identity`` (Dropout at inference);
 * the ``save/`` subgraph (``SaveV2`` / ``RestoreV2`` + ``AssignVariableOp`` → ``save/restore_all``) and a
   ``SaverDef`` pointing at it, so a TF1 loader restores ``variables/variables`` by running the restore op;
@@ -182,6 +182,10 @@ def build_graph(model, input_name="Placeholder", input_shape=None):
             y = _activation(g, nm, x, layer.activation)
         elif isinstance(layer, L.MaxPooling2D):
             y = g.node(f"{nm}/MaxPool", "MaxPool", [x], ksize=A.ints([1, *layer.pool_size, 1]),
+                       strides=A.ints([1, *layer.strides, 1]), padding=A.s(layer.padding.upper()),
+                       data_format=A.s("NHWC"), **_float_attrs())
+        elif isinstance(layer, L.AveragePooling2D):
+            y = g.node(f"{nm}/AvgPool", "AvgPool", [x], ksize=A.ints([1, *layer.pool_size, 1]),
                        strides=A.ints([1, *layer.strides, 1]), padding=A.s(layer.padding.upper()),
                        data_format=A.s("NHWC"), **_float_attrs())
         elif isinstance(layer, L.BatchNormalization):
@@ -367,6 +371,10 @@ def run_graph(graph_nodes, feeds: dict, variables: dict, fetch: str):
             return xs[0] + xs[1]
         if op == "Relu":
             return np.maximum(xs[0], 0)
+        if op == "Tanh":
+            return np.tanh(xs[0])
+        if op == "Sigmoid":
+            return 1.0 / (1.0 + np.exp(-xs[0]))
         if op == "Softmax":
             e = np.exp(xs[0] - xs[0].max(-1, keepdims=True))
             return e / e.sum(-1, keepdims=True)
@@ -374,6 +382,8 @@ def run_graph(graph_nodes, feeds: dict, variables: dict, fetch: str):
             return xs[0] @ xs[1]
         if op == "MaxPool":
             return _maxpool(xs[0], at["ksize"][1:3], at["strides"][1:3], at["padding"])
+        if op == "AvgPool":
+            return _avgpool(xs[0], at["ksize"][1:3], at["strides"][1:3], at["padding"])
         if op == "FusedBatchNormV3":
             x, sc, of, mu, var = xs
             return (x - mu) / np.sqrt(var + at["epsilon"]) * sc + of
@@ -429,3 +439,23 @@ def _maxpool(x, ksize, strides, padding):
         for j in range(kw):
             out = np.maximum(out, x[:, i: i + sh * (Ho - 1) + 1: sh, j: j + sw * (Wo - 1) + 1: sw, :])
     return out
+
+
+def _avgpool(x, ksize, strides, padding):
+    """TF AvgPool: with SAME padding a window is averaged over its elements inside the image."""
+    B, H, W, C = x.shape
+    kh, kw = ksize
+    sh, sw = strides
+    cnt = np.ones((1, H, W, 1))
+    if padding == "SAME":
+        (pt, pb), (pl, pr) = _same_pads(H, kh, sh), _same_pads(W, kw, sw)
+        x = np.pad(x, [(0, 0), (pt, pb), (pl, pr), (0, 0)])
+        cnt = np.pad(cnt, [(0, 0), (pt, pb), (pl, pr), (0, 0)])
+    Ho, Wo = (x.shape[1] - kh) // sh + 1, (x.shape[2] - kw) // sw + 1
+    out = np.zeros((B, Ho, Wo, C))
+    n = np.zeros((1, Ho, Wo, 1))
+    for i in range(kh):
+        for j in range(kw):
+            out += x[:, i: i + sh * (Ho - 1) + 1: sh, j: j + sw * (Wo - 1) + 1: sw, :]
+            n += cnt[:, i: i + sh * (Ho - 1) + 1: sh, j: j + sw * (Wo - 1) + 1: sw, :]
+    return out / n

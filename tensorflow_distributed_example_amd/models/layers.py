@@ -279,9 +279,7 @@ class Dense(Layer):
         return dict(name=self.name, units=self.units, activation=self.activation, use_bias=self.use_bias)
 
 
-class MaxPooling2D(Layer):
-    _prefix = "max_pooling2d"
-
+class _Pooling2D(Layer):
     def __init__(self, pool_size=(2, 2), strides=None, padding="valid", **kw):
         super().__init__(**kw)
         self.pool_size = _tuple2(pool_size)
@@ -296,6 +294,13 @@ class MaxPooling2D(Layer):
             return ((H - ph) // sh + 1, (W - pw) // sw + 1, C)
         return (-(-H // sh), -(-W // sw), C)
 
+    def get_config(self):
+        return dict(name=self.name, pool_size=self.pool_size, strides=self.strides, padding=self.padding)
+
+
+class MaxPooling2D(_Pooling2D):
+    _prefix = "max_pooling2d"
+
     def ref_call(self, x, W, training, rng=None, state_updates=None):
         xc = x.permute(0, 3, 1, 2)
         if self.padding == "same":
@@ -305,8 +310,21 @@ class MaxPooling2D(Layer):
         y = F.max_pool2d(xc, self.pool_size, self.strides)
         return y.permute(0, 2, 3, 1)
 
-    def get_config(self):
-        return dict(name=self.name, pool_size=self.pool_size, strides=self.strides, padding=self.padding)
+
+class AveragePooling2D(_Pooling2D):
+    _prefix = "average_pooling2d"
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        xc = x.permute(0, 3, 1, 2)
+        if self.padding == "same":   # Keras: a window averages over its elements inside the image only
+            (pt, pb) = tf_same_pads(x.shape[1], self.pool_size[0], self.strides[0])
+            (pl, pr) = tf_same_pads(x.shape[2], self.pool_size[1], self.strides[1])
+            ones = F.pad(torch.ones_like(xc[:1, :1]), (pl, pr, pt, pb))
+            cnt = F.avg_pool2d(ones, self.pool_size, self.strides, divisor_override=1)
+            y = F.avg_pool2d(F.pad(xc, (pl, pr, pt, pb)), self.pool_size, self.strides, divisor_override=1) / cnt
+        else:
+            y = F.avg_pool2d(xc, self.pool_size, self.strides)
+        return y.permute(0, 2, 3, 1)
 
 
 class GlobalAveragePooling2D(Layer):
@@ -491,9 +509,9 @@ class Add(Layer):
         return out
 
 
-LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, Dense, MaxPooling2D, GlobalAveragePooling2D,
-                                         ZeroPadding2D, Flatten, Reshape, Activation, ReLU, Dropout,
-                                         BatchNormalization, Add]}
+LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, Dense, MaxPooling2D, AveragePooling2D,
+                                         GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
+                                         Dropout, BatchNormalization, Add]}
 
 
 def from_config(cls_name, cfg):

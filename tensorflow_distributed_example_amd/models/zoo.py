@@ -9,6 +9,7 @@ Models for the remaining BASELINE.json configs (not in the reference; SURVEY.md 
 
 * ``lenet5()``    — "MNIST LeNet-5 CNN bf16, MirroredStrategy on 1 MI355X": LeNet-5 with ReLU and max
   pooling, 61,706 trainable params.
+* ``lenet5_classic()`` — the same network with the original tanh activations and 2x2 average pooling.
 * ``mnist_mlp()`` — "tf2_mnist_distributed.py dense MLP on CPU, MirroredStrategy devices=1":
   Flatten · Dense(128, relu) · Dense(10), 101,770 trainable params.
 * ``resnet18()``  — "Synthetic 224x224x3 ResNet-18 bf16 on 8xMI355X".
@@ -70,6 +71,20 @@ def lenet5(name=None):
         L.Flatten(),
         L.Dense(120, activation="relu"),
         L.Dense(84, activation="relu"),
+        L.Dense(10),
+    ], name=name)
+
+
+def lenet5_classic(name=None):
+    """LeCun's LeNet-5 as published: tanh activations and 2x2 average pooling (float32 policy)."""
+    return Sequential([
+        L.Conv2D(6, 5, padding="same", activation="tanh", input_shape=(28, 28, 1)),
+        L.AveragePooling2D(),
+        L.Conv2D(16, 5, activation="tanh"),
+        L.AveragePooling2D(),
+        L.Flatten(),
+        L.Dense(120, activation="tanh"),
+        L.Dense(84, activation="tanh"),
         L.Dense(10),
     ], name=name)
 

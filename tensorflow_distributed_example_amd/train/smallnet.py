@@ -2,13 +2,21 @@
 
 Model families: BASELINE.json config 2 (MNIST LeNet-5, ``zoo.lenet5``) and config 1's dense MLP
 (``tf2_mnist_distributed.py``'s plumbing model, ``zoo.mnist_mlp``); any Sequential chain of
-``Conv2D(stride 1, same/valid, relu|linear) [MaxPooling2D(2)]`` stages, ``Flatten``/``Reshape``,
-``Dense(relu|linear)`` layers and a ``Dense`` head (logits, or softmax fed to the probability form of
-``SparseCategoricalCrossentropy``) whose per-image activations fit in one workgroup's LDS.  A
-``Dropout`` may follow a Conv2D stage without a pool, a MaxPooling2D or a non-head Dense (a Flatten /
-Reshape or a standalone ``Activation("relu")`` may sit in between): the kernel multiplies that
-activation, and in the backward the gradient that lands on it, by the Philox keep scale in LDS -- the
-layer-wise plan's mask, element for element (``train/elementwise_ids.py``), regenerated, never stored.
+``Conv2D(stride 1, same/valid, act) [MaxPooling2D(2) | AveragePooling2D(2)]`` stages,
+``Flatten``/``Reshape``, ``Dense(act)`` layers and a ``Dense`` head (logits, or softmax fed to the
+probability form of ``SparseCategoricalCrossentropy``) whose per-image activations fit in one
+workgroup's LDS; ``act`` is linear, relu, tanh or sigmoid, on the layer or as a standalone
+``Activation`` behind a linear one (``zoo.lenet5_classic``: LeCun's tanh / average-pool LeNet-5).  The
+backward needs nothing stored for them: each gradient overwrites the activation it belongs to, and the
+derivative is a function of that activation's own output (``y > 0``, ``1 - y^2``, ``y (1 - y)``), read
+just before the overwrite.  A ``Dropout`` may follow a Conv2D stage without a pool, a pooling layer or
+a non-head Dense (a Flatten / Reshape or a standalone ``Activation("relu")`` may sit in between): the
+kernel multiplies that activation, and in the backward the gradient that lands on it, by the Philox
+keep scale in LDS -- the layer-wise plan's mask, element for element (``train/elementwise_ids.py``),
+regenerated, never stored.
+
+Known limit: a ``Dropout`` directly on a tanh or sigmoid output is not matched (the dropped activation
+in LDS no longer gives the derivative without the keep scale); such a model is left to the other plans.
 
 A training step is two HIP launches (``csrc/kernels/smallnet.hip``): one workgroup per image runs the
 forward, the loss and the whole input-gradient chain out of LDS and leaves per-image conv weight
@@ -34,8 +42,10 @@ from ..models import layers as L
 from .elementwise_ids import dropout_ids
 from .program import OptimizerKernel, ReplicaPlan
 
-CONV, POOL, DENSE = 0, 1, 2
-_FIELDS = ("kind", "relu", "mask_in", "need_gin", "H", "W", "C", "Ho", "Wo", "Co", "kh", "kw", "pt", "pl",
+CONV, POOL, DENSE, AVGPOOL = 0, 1, 2, 3
+LINEAR, RELU, TANH, SIGMOID = 0, 1, 2, 3        # activation codes of the ``act`` / ``mask_in`` plan fields
+_ACT = {None: LINEAR, "relu": RELU, "tanh": TANH, "sigmoid": SIGMOID}
+_FIELDS = ("kind", "act", "mask_in", "need_gin", "H", "W", "C", "Ho", "Wo", "Co", "kh", "kw", "pt", "pl",
            "w_off", "b_off", "in", "out", "wl", "part", "xo", "go",
            "drop_rate", "drop_seed_lo", "drop_seed_hi", "drop_lid", "drop_n")
 
@@ -63,8 +73,9 @@ def _chain(model):
 
 
 def match_smallnet(model, loss):
-    """Per-layer description of a supported model, or None.  One entry per Conv2D / MaxPooling2D / Dense;
-    ``drop`` is the Dropout layer applied to the entry's output (after its ReLU), or None."""
+    """Per-layer description of a supported model, or None.  One entry per Conv2D / pooling layer / Dense;
+    ``relu`` is the entry's activation code (LINEAR, RELU, TANH, SIGMOID), ``drop`` the Dropout layer applied
+    to the entry's output (after its activation), or None."""
     if not isinstance(loss, SparseCategoricalCrossentropy):
         return None
     chain = _chain(model)
@@ -89,13 +100,13 @@ def match_smallnet(model, loss):
                 return None
             continue
         if isinstance(layer, L.Activation):
-            if (layer.activation != "relu" or not spec or spec[-1]["kind"] == POOL or spec[-1]["relu"]
-                    or spec[-1]["drop"] is not None):
+            if (layer.activation not in ("relu", "tanh", "sigmoid") or not spec
+                    or spec[-1]["kind"] in (POOL, AVGPOOL) or spec[-1]["relu"] or spec[-1]["drop"] is not None):
                 return None
-            spec[-1]["relu"] = 1
+            spec[-1]["relu"] = _ACT[layer.activation]
             continue
         if isinstance(layer, L.Conv2D):
-            if layer.strides != (1, 1) or layer.activation not in (None, "linear", "relu"):
+            if layer.strides != (1, 1) or layer.activation not in _ACT:
                 return None
             H, W, C = shape
             (pt, pb), (pl, pr) = layer.pads((H, W, C))
@@ -103,30 +114,33 @@ def match_smallnet(model, loss):
             if Ho < 1 or Wo < 1:
                 return None
             spec.append(dict(kind=CONV, layer=layer, inp=(H, W, C), outp=(Ho, Wo, Co),
-                             relu=int(layer.activation == "relu"), pt=pt, pl=pl, pb=pb, pr=pr, drop=None))
+                             relu=_ACT[layer.activation], pt=pt, pl=pl, pb=pb, pr=pr, drop=None))
             shape = (Ho, Wo, Co)
             continue
-        if isinstance(layer, L.MaxPooling2D):
+        if isinstance(layer, (L.MaxPooling2D, L.AveragePooling2D)):
             if layer.pool_size != (2, 2) or layer.strides != (2, 2) or layer.padding != "valid":
                 return None
             H, W, C = shape
             if H < 2 or W < 2 or not spec or spec[-1]["kind"] != CONV:
                 return None
-            if spec[-1]["drop"] is not None:   # the pool backward recomputes the argmax from the conv output
+            if spec[-1]["drop"] is not None:   # the pool backward reads the conv output (argmax, derivative)
                 return None
-            spec.append(dict(kind=POOL, layer=layer, inp=shape, outp=(H // 2, W // 2, C), relu=0, drop=None))
+            kind = POOL if isinstance(layer, L.MaxPooling2D) else AVGPOOL
+            spec.append(dict(kind=kind, layer=layer, inp=shape, outp=(H // 2, W // 2, C), relu=0, drop=None))
             shape = (H // 2, W // 2, C)
             continue
         if isinstance(layer, L.Dense):
-            if shape[0] != 1 or shape[1] != 1 or layer.activation not in (None, "linear", "relu", "softmax"):
+            if shape[0] != 1 or shape[1] != 1 or layer.activation not in (*_ACT, "softmax"):
                 return None
             spec.append(dict(kind=DENSE, layer=layer, inp=shape, outp=(1, 1, layer.units),
-                             relu=int(layer.activation == "relu"), drop=None))
+                             relu=_ACT.get(layer.activation, LINEAR), drop=None))
             shape = (1, 1, layer.units)
             continue
         if isinstance(layer, L.Dropout):
             # on the output of the last entry; not on the raw input, not twice on one activation
             if not spec or spec[-1]["drop"] is not None or not 0.0 <= layer.rate < 1.0:
+                return None
+            if spec[-1]["relu"] in (TANH, SIGMOID):   # the derivative is read from the undropped output
                 return None
             spec[-1]["drop"] = layer
             continue
@@ -134,7 +148,7 @@ def match_smallnet(model, loss):
     if not spec or spec[-1]["kind"] != DENSE:
         return None
     head = spec[-1]["layer"]
-    if head.activation == "relu" or spec[-1]["relu"] or spec[-1]["drop"] is not None:
+    if head.activation in ("relu", "tanh", "sigmoid") or spec[-1]["relu"] or spec[-1]["drop"] is not None:
         return None
     if (head.activation == "softmax") == bool(loss.from_logits):
         return None
@@ -185,12 +199,12 @@ class SmallNetPlan(ReplicaPlan):
             H, W, C = s["inp"]
             Ho, Wo, Co = s["outp"]
             r = dict.fromkeys(_FIELDS, 0)
-            r.update(kind=s["kind"], relu=s["relu"], H=H, W=W, C=C, Ho=Ho, Wo=Wo, Co=Co, b_off=-1,
+            r.update(kind=s["kind"], act=s["relu"], H=H, W=W, C=C, Ho=Ho, Wo=Wo, Co=Co, b_off=-1,
                      **{"in": prev_out})
             r["need_gin"] = int(i > 0)
-            r["mask_in"] = int(prev_kind in (CONV, DENSE) and prev_relu == 1)
-            if s["kind"] == POOL:
-                r["mask_in"] = int(prev_relu == 1)    # routes to the conv output's maxima, ReLU mask there
+            # the code of the activation whose output is this layer's `in` buffer (a pool: the conv before it,
+            # whose derivative it applies at the window elements the gradient is routed to)
+            r["mask_in"] = prev_relu if prev_kind in (CONV, DENSE) else LINEAR
             if s["kind"] in (CONV, DENSE):
                 r["w_off"] = seg[f"{lay.name}/kernel"].offset
                 if lay.use_bias:
