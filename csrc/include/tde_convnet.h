@@ -60,6 +60,36 @@ __device__ __forceinline__ void fwd_snap_head(const FwdArgs& a, int nthreads) {
   }
 }
 
+// The same copy in two halves for a prologue that waits once: issue() loads this thread's elements
+// (tid + k*NT, k < N; N*NT covers the largest snapshot, hC = 16) with every load in flight at once,
+// store() writes them after the caller's common wait.  Straight-line: an element past the end loads
+// the last element (index clamped, never an address outside the sources) and is not stored.
+template <int NT>
+struct SnapHead {
+  static constexpr int N = (HD + HD * 16 + 16 + NT - 1) / NT;
+  float v[N];
+  __device__ __forceinline__ static bool mine(const FwdArgs& a) { return a.hsnap && blockIdx.x == 0 && blockIdx.y == 0; }
+  __device__ __forceinline__ void issue(const FwdArgs& a) {
+    const int C = a.hC, n = HD + HD * C + C;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const int i = min((int)threadIdx.x + k * NT, n - 1);
+      // b1 is nullable: its slots then read W2's first elements and store 0
+      const float* src = i < HD ? (a.hsrc_b1 ? a.hsrc_b1 + i : a.hsrc_w2 + i)
+                                : (i < HD + HD * C ? a.hsrc_w2 + (i - HD) : a.hsrc_b2 + (i - HD - HD * C));
+      v[k] = *src;
+    }
+  }
+  __device__ __forceinline__ void store(const FwdArgs& a) const {
+    const int C = a.hC, n = HD + HD * C + C;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const int i = (int)threadIdx.x + k * NT;
+      if (i < n) a.hsnap[i] = (i < HD && !a.hsrc_b1) ? 0.f : v[k];
+    }
+  }
+};
+
 // The input rows a workgroup's pooled positions touch (<= XR rows of <= XW floats per image)
 // are staged into LDS with coalesced float4 loads: gathering 4x4 patches straight from HBM
 // puts 64 distinct cache lines behind every load instruction.
@@ -101,6 +131,47 @@ __device__ __forceinline__ void fwd_stage_x(const FwdArgs& a, float* xr, int b0,
 
 // Forward prologue, part 2: the conv weights in effect for this step -> wcs (with the
 // deferred update applied while *pend).
+// In two halves, so that a prologue can put these loads in flight with its other loads and wait once:
+// ConvOperand::issue() holds every load of element i (the weight and, in the fused step, the gradient
+// replicas and the slots: straight-line, a replica past grep reads replica grep-1 and counts as 0),
+// conv_flags_issue() the two scalars of the deferred update, ConvOperand::finish() the arithmetic.
+struct ConvOperand {
+  float w, g[kMaxGrep], m, v;
+  __device__ __forceinline__ void issue(const FwdArgs& a, int i) {
+    const bool isb = i >= 9 * CC;
+    const int j = isb ? i - 9 * CC : i;
+    const float* wp = isb ? a.bc + j : a.wc + j;
+    w = *wp;
+    if (a.pend) {
+      const float* gp = isb ? a.gbc + j : a.gwc + j;
+#pragma unroll
+      for (int r = 0; r < kMaxGrep; ++r) g[r] = gp[min(r, a.grep - 1) * a.grep_stride];
+      // a slot the optimizer does not have reads the weight again and counts as 0
+      m = *(a.h.kind != kOptSGD ? (isb ? a.mbc + j : a.mwc + j) : wp);
+      v = *(a.h.kind == kOptAdam ? (isb ? a.vbc + j : a.vwc + j) : wp);
+    }
+  }
+  // the weight in effect: the optimizer step of w while the update is pending (replicas summed in order)
+  __device__ __forceinline__ float finish(const FwdArgs& a, int pend, long long iterations) {
+    if (!a.pend) return w;
+    float gs = g[0];
+#pragma unroll
+    for (int r = 1; r < kMaxGrep; ++r) gs += r < a.grep ? g[r] : 0.f;
+    const long long t = a.h.kind == kOptAdam ? iterations : 0;
+    float ms = a.h.kind != kOptSGD ? m : 0.f, vs = a.h.kind == kOptAdam ? v : 0.f;
+    return pend ? opt_step(a.h, opt_lr_t(a.h, t), w, gs, ms, vs) : w;
+  }
+};
+__device__ __forceinline__ void conv_flags_issue(const FwdArgs& a, int& pend, long long& iterations) {
+  pend = 0;
+  iterations = 0;
+  if (a.pend) {
+    pend = *a.pend;
+    iterations = *a.iterations;
+  }
+}
+
+// The two halves in one call, element by element (the bf16 forward: its prologue is not restructured)
 __device__ __forceinline__ void fwd_stage_conv(const FwdArgs& a, float* wcs, int nthreads) {
   for (int i = threadIdx.x; i < kConvW; i += nthreads) {
     const bool isb = i >= 9 * CC;
@@ -302,19 +373,67 @@ __device__ __forceinline__ void zero_other_parity(const BwdArgs& a, int tid) {
   for (int i = beg + tid; i < end; i += 1024) reinterpret_cast<float4*>(a.hzero)[i] = float4{0.f, 0.f, 0.f, 0.f};
 }
 
+// An opaque copy of threadIdx.x for the chunk loops of the backward: the addresses computed from it (all
+// loop-invariant: one per load and per LDS access) are computed again in each iteration and not kept in
+// registers across the loop, where they pushed the kernels into scratch.
+__device__ __forceinline__ int opaque_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
 // hpre[row][c4..c4+3] summed over the replicas (loads issued together).  More than 4 replicas: the
 // deterministic mode (TDE_DETERMINISTIC: one replica per forward workgroup, each written by exactly one
 // add into zeros), summed in replica order.
-__device__ __forceinline__ float4 load_hpre(const BwdArgs& a, int row, int c4) {
-  constexpr int kMaxRep = 8;
-  if (a.hrep > kMaxRep) {
-    float4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < a.hrep; ++r) {
-      const float4 v = *reinterpret_cast<const float4*>(a.hpre + (size_t)r * a.hrep_stride + (size_t)row * HD + c4);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+// HpreRep<N> holds hrep <= N replicas in N float4 (N a compile-time count: 4 replicas cost 16 registers,
+// not the 32 of the largest count): issue() is straight-line, a replica past hrep reads replica hrep-1
+// and counts as 0 in sum() (replica order).  load_hpre_sw() picks the count by a uniform switch on hrep.
+constexpr int kMaxRep = 8;
+template <int N>
+struct HpreRep {
+  float4 v[N];
+  __device__ __forceinline__ void issue(const BwdArgs& a, int row, int c4) {
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+      v[r] = *reinterpret_cast<const float4*>(a.hpre + (size_t)min(r, a.hrep - 1) * a.hrep_stride + (size_t)row * HD + c4);
+  }
+  __device__ __forceinline__ float4 sum(const BwdArgs& a) const {
+    float4 s = v[0];
+#pragma unroll
+    for (int r = 1; r < N; ++r) {
+      const bool on = r < a.hrep;
+      s.x += on ? v[r].x : 0.f; s.y += on ? v[r].y : 0.f; s.z += on ? v[r].z : 0.f; s.w += on ? v[r].w : 0.f;
     }
     return s;
   }
+};
+__device__ __forceinline__ float4 load_hpre_loop(const BwdArgs& a, int row, int c4) {
+  float4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < a.hrep; ++r) {
+    const float4 v = *reinterpret_cast<const float4*>(a.hpre + (size_t)r * a.hrep_stride + (size_t)row * HD + c4);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  return s;
+}
+template <int N>
+__device__ __forceinline__ float4 load_hpre_n(const BwdArgs& a, int row, int c4) {
+  HpreRep<N> h;
+  h.issue(a, row, c4);
+  return h.sum(a);
+}
+// The replica count picked by a uniform switch (float32 kernels)
+__device__ __forceinline__ float4 load_hpre_sw(const BwdArgs& a, int row, int c4) {
+  if (a.hrep > kMaxRep) return load_hpre_loop(a, row, c4);
+  switch (a.hrep) {
+    case 1: return load_hpre_n<1>(a, row, c4);
+    case 2: return load_hpre_n<2>(a, row, c4);
+    case 3: case 4: return load_hpre_n<4>(a, row, c4);
+    default: return load_hpre_n<8>(a, row, c4);
+  }
+}
+// kMaxRep slots whatever hrep is (the bf16 kernels)
+__device__ __forceinline__ float4 load_hpre(const BwdArgs& a, int row, int c4) {
+  if (a.hrep > kMaxRep) return load_hpre_loop(a, row, c4);
   float4 v[kMaxRep];
 #pragma unroll
   for (int r = 0; r < kMaxRep; ++r)
@@ -400,39 +519,43 @@ __device__ __forceinline__ f32x4 head_dh(const BwdArgs& a, int nb, const HeadLds
   return gh;
 }
 
+// Fused step: flat index of the i-th (of 4) head variable that thread tid of the head workgroup updates, -1:
+// none.  waves 0..3: W2[wave*16 + 4fq + i][fr] (the dW2 tile layout); wave 4: b2[fr]; wave 5: b1[lane].
+// Computed where it is used (from opaque_tid()), not held across the chunk loop.
+__device__ __forceinline__ long long head_var(const BwdArgs& a, int tid, int i) {
+  const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4, C = a.C;
+  if (wave < 4 && fr < C) return a.off_w2 + (long long)(wave * 16 + fq * 4 + i) * C + fr;
+  if (i == 0 && wave == 4 && fq == 0 && fr < C) return a.off_b2 + fr;
+  if (i == 0 && wave == 5 && a.off_b1 >= 0) return a.off_b1 + lane;
+  return -1;
+}
+
 // The head workgroup: loss / accuracy, dW2 = h^T . dl, db2, db1 over all chunks, then stored (MODE 0)
 // or updated (fused step; with the previous step's deferred conv update and the flags).
 // db1p: 256 floats of LDS scratch outside the head areas.
-template <int MODE>
+// LEAN (the float32 kernels, which must stay out of scratch): thread indices from opaque_tid() inside the
+// chunk loop and at the update, replica slots by switch.
+template <int MODE, bool LEAN = false>
 __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& l, float* db1p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
   const int fr = lane & 15, fq = lane >> 4, C = a.C;
-  const int hr = tid >> 4, hc4 = (tid & 15) * 4;
-  const float4 b1v = a.b1 ? *reinterpret_cast<const float4*>(a.b1 + hc4) : float4{0.f, 0.f, 0.f, 0.f};
+  const float4 b1v = a.b1 ? *reinterpret_cast<const float4*>(a.b1 + (tid & 15) * 4) : float4{0.f, 0.f, 0.f, 0.f};
 
-  // fused step: the variables this workgroup updates, loaded now.  waves 0..3: W2[wave*16 + 4fq + i][fr]
-  // (the dW2 tile layout); wave 4: b2[fr]; wave 5: b1[lane]
-  long long e[4] = {-1, -1, -1, -1};
-  if (wave < 4 && fr < C) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) e[i] = a.off_w2 + (long long)(wave * 16 + fq * 4 + i) * C + fr;
-  } else if (wave == 4 && fq == 0 && fr < C) {
-    e[0] = a.off_b2 + fr;
-  } else if (wave == 5 && a.off_b1 >= 0) {
-    e[0] = a.off_b1 + lane;
-  }
+  // fused step: the variables this workgroup updates (head_var), loaded now
   float hwv[4] = {0.f, 0.f, 0.f, 0.f}, hmv[4] = {0.f, 0.f, 0.f, 0.f}, hvv[4] = {0.f, 0.f, 0.f, 0.f};
   long long t_it = 0;
   FlatPrefetch<1> cp;
   int cpend = 0;
   if (MODE != 0) {
     t_it = *a.iterations;
+    const int tl = LEAN ? opaque_tid() : (int)threadIdx.x;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if (e[i] < 0) continue;
-      hwv[i] = a.hw[e[i]];
-      if (MODE == 2 && a.h.kind != kOptSGD) hmv[i] = a.hm[e[i]];
-      if (MODE == 2 && a.h.kind == kOptAdam) hvv[i] = a.hv[e[i]];
+      const long long e = head_var(a, tl, i);
+      if (e < 0) continue;
+      hwv[i] = a.hw[e];
+      if (MODE == 2 && a.h.kind != kOptSGD) hmv[i] = a.hm[e];
+      if (MODE == 2 && a.h.kind == kOptAdam) hvv[i] = a.hv[e];
     }
     if (a.commit.nr > 0) {
       cpend = *a.commit.pend;
@@ -444,8 +567,12 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
   float db1acc = 0.f, db2acc = 0.f, la = 0.f, ca = 0.f, na = 0.f;
   for (int b0 = 0; b0 < a.B; b0 += 64) {
     const int nb = min(64, a.B - b0);
+    // this iteration's own copies of the thread indices (opaque_tid())
+    const int tid = LEAN ? opaque_tid() : (int)threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+    const int hr = tid >> 4, hc4 = (tid & 15) * 4;
     float4 hv = {0.f, 0.f, 0.f, 0.f};
-    if (hr < nb) hv = load_hpre(a, b0 + hr, hc4);
+    if (hr < nb) hv = LEAN ? load_hpre_sw(a, b0 + hr, hc4) : load_hpre(a, b0 + hr, hc4);
     const int lab = (tid < nb) ? a.labels[b0 + tid] : 0;
     head_stage(a, hv, b1v, hr, hc4, nb, l.hs);
     if (tid < 64) l.labs[tid] = lab;
@@ -502,13 +629,15 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
     return;
   }
   const float lr_t = opt_lr_t(a.h, t_it);
+  const int tl = LEAN ? opaque_tid() : (int)threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (e[i] < 0) continue;
+    const long long e = head_var(a, tl, i);
+    if (e < 0) continue;
     float m = hmv[i], v = hvv[i];
-    a.hw[e[i]] = opt_step(a.h, lr_t, hwv[i], gv[i], m, v);
-    if (MODE == 2 && a.h.kind != kOptSGD) a.hm[e[i]] = m;
-    if (MODE == 2 && a.h.kind == kOptAdam) a.hv[e[i]] = v;
+    a.hw[e] = opt_step(a.h, lr_t, hwv[i], gv[i], m, v);
+    if (MODE == 2 && a.h.kind != kOptSGD) a.hm[e] = m;
+    if (MODE == 2 && a.h.kind == kOptAdam) a.hv[e] = v;
   }
   // the previous step's conv update (its forward used it on the fly; this launch does not read the
   // conv weights): commit it, clear its flag; flag this step's update (the trunk's atomics)

@@ -49,29 +49,35 @@ __device__ __forceinline__ int k8_col(int fq, int i) { return fq * 8 + 4 * ((i +
 // ... and of a 64-wide (16 k per lane group) row
 __device__ __forceinline__ int k16_col(int fq, int i) { return fq * 16 + 4 * ((i + fq) & 3); }
 
-// The <= XR input rows of the workgroup's FB images -> xr (coalesced float4 loads, all issued before
-// the first LDS store: one round trip; the 16-byte-aligned image stride takes whole float4 stores).
-__device__ __forceinline__ void fwd32_stage_x(const FwdArgs& a, float* xr, int b0, int py0, int nrows) {
-  const int W = a.W, H = a.H;
-  const int istride = fwd32_istride(W);
-  const int n4 = nrows * W / 4;  // float4 per image
-  constexpr int kU = 3;          // 16 images x 6 rows x 32 floats = 768 float4: one pass of 256 threads
-  for (int i0 = threadIdx.x; i0 < FB * n4; i0 += kU * 256) {
-    float4 v[kU];
+// The <= XR input rows of the workgroup's FB images -> xr, in two halves: issue() the coalesced float4
+// loads (16 images x 6 rows x 32 floats = 768 float4 at most: kU per thread, one pass of 256 threads),
+// store() after the prologue's common wait (the 16-byte-aligned image stride takes whole float4 stores).
+struct Fwd32X {
+  static constexpr int kU = 3;
+  static_assert(FB * XR * XW / 4 <= kU * 256, "one pass of the workgroup stages the rows");
+  float4 v[kU];
+  __device__ __forceinline__ void issue(const FwdArgs& a, int b0, int py0, int nrows) {
+    const int W = a.W, H = a.H;
+    const int n4 = nrows * W / 4;  // float4 per image
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      const int i = i0 + u * 256, bl = i / n4, q = i - bl * n4;
+      const int i = threadIdx.x + u * 256, bl = i / n4, q = i - bl * n4;
       v[u] = float4{0.f, 0.f, 0.f, 0.f};
       if (i < FB * n4 && b0 + bl < a.B)
         v[u] = *reinterpret_cast<const float4*>(a.x + (size_t)(b0 + bl) * H * W + (size_t)(2 * py0) * W + q * 4);
     }
+  }
+  __device__ __forceinline__ void store(const FwdArgs& a, float* xr, int nrows) const {
+    const int W = a.W;
+    const int istride = fwd32_istride(W);
+    const int n4 = nrows * W / 4;
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      const int i = i0 + u * 256, bl = i / n4, q = i - bl * n4;
+      const int i = threadIdx.x + u * 256, bl = i / n4, q = i - bl * n4;
       if (i < FB * n4) *reinterpret_cast<float4*>(xr + bl * istride + q * 4) = v[u];
     }
   }
-}
+};
 
 __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   constexpr int NT = 256;
@@ -79,11 +85,13 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   float* As = reinterpret_cast<float*>(fsm);                                  // [FB][AS32] pooled tile
   float* xr = reinterpret_cast<float*>(fsm + FB * AS32 * 4);                  // [FB][XR][W]
   float* wcs = reinterpret_cast<float*>(fsm + FB * AS32 * 4 + kXr32Bytes);    // [10][CC]
+  // the two scalars of the deferred update, read ahead of the kernel's first store (scalar loads: nothing
+  // waits for them before the prologue's common wait)
+  int pendv;
+  long long iterv;
+  conv_flags_issue(a, pendv, iterv);
   stamp(a.stamps, 0);
   if (a.inc_iter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.inc_iter, 1ull);
-  if (a.fly_count && a.pend && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && *a.pend)
-    atomicAdd(a.fly_count, 1ull);
-  fwd_snap_head(a, NT);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
   const int W = a.W, H = a.H;
@@ -95,21 +103,35 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   const float* W1 = reinterpret_cast<const float*>(a.W1);
   float* Pt = reinterpret_cast<float*>(a.Pt);
 
-  // B fragments first (independent of the staging below, so their round trip overlaps it):
-  // W1[kp*32 + k][nt*16 + fr] for this lane's 8 k of each position (f32 master, [K][HD])
+  // ---- prologue: every global load is issued before the first wait and the first LDS store (one round
+  // trip).  In the order of use: the image rows and the conv operands (phase 1; all kConvW = 320
+  // elements in one pass, threads below 64 hold two), the head snapshot's sources (workgroup (0,0)),
+  // then the B fragments (phase 2): W1[kp*32 + k][nt*16 + fr] for this lane's 8 k of each position
+  // (f32 master, [K][HD]).
+  static_assert(kConvW > NT && kConvW <= NT + 64, "wave 0 holds the conv operands past the first NT");
+  Fwd32X xst;
+  xst.issue(a, b0, py0, nrows);
+  ConvOperand cv0, cv1;
+  cv0.issue(a, threadIdx.x);
+  if (wave == 0) cv1.issue(a, NT + min((int)threadIdx.x, kConvW - NT - 1));
+  SnapHead<NT> snap;
+  const bool snap_wg = SnapHead<NT>::mine(a);
+  if (snap_wg) snap.issue(a);
   const int nt = wave;
   float wfr[FG][8];
 #pragma unroll
   for (int ks = 0; ks < FG; ++ks) {
-    const int kp = p0 + ks;
+    const int kp = min(p0 + ks, P - 1);   // positions past P read the last one and count as 0 below
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        wfr[ks][4 * i + j] = kp < P ? W1[(size_t)(kp * CC + k8_col(fq, i) + j) * a.ldw1 + nt * 16 + fr] : 0.f;
+      for (int j = 0; j < 4; ++j) wfr[ks][4 * i + j] = W1[(size_t)(kp * CC + k8_col(fq, i) + j) * a.ldw1 + nt * 16 + fr];
   }
-  fwd32_stage_x(a, xr, b0, py0, nrows);
-  fwd_stage_conv(a, wcs, NT);
+  xst.store(a, xr, nrows);
+  wcs[threadIdx.x] = cv0.finish(a, pendv, iterv);
+  if (wave == 0 && threadIdx.x < kConvW - NT) wcs[NT + threadIdx.x] = cv1.finish(a, pendv, iterv);
+  if (snap_wg) snap.store(a);
+  if (a.fly_count && pendv && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.fly_count, 1ull);
   stamp(a.stamps, 1);
   lds_barrier();
 
@@ -142,6 +164,11 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   lds_barrier();
   stamp(a.stamps, 3);
 
+  // the fragments of positions past P were loaded from the last position: they count as 0
+#pragma unroll
+  for (int ks = 0; ks < FG; ++ks)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) wfr[ks][i] = p0 + ks < P ? wfr[ks][i] : 0.f;
   // ---- phase 2: hpre[16 x 64] += As(16 x FG*32) . W1(FG*32 x 64) on the f32 MFMA; wave = column tile nt,
   // one accumulator per position (independent chains keep the pipe issuing), summed before the adds:
   // the FG positions' split-K partial sums meet in registers, not in memory
@@ -187,6 +214,61 @@ constexpr int kLab32 = kB2s32 + kB2Bytes;
 constexpr int kBwd32Lds = kLab32 + kLabBytes;
 static_assert(kBwd32Lds <= 160 * 1024, "backward LDS exceeds a CU");
 
+// The thread's indices from an opaque copy of threadIdx.x (opaque_tid(): nothing computed from them is
+// kept in registers across the chunk loop).
+__device__ __forceinline__ void bwd32_ids(int& tid, int& lane, int& wave, int& fr, int& fq) {
+  const int t = opaque_tid();
+  tid = t;
+  lane = t & 63;
+  wave = t >> 6;
+  fr = lane & 15;
+  fq = lane >> 4;
+}
+
+// One image chunk's global operands of a trunk workgroup, in registers.
+struct Bwd32Chunk {
+  float4 hv;      // hpre row hr, units hc4.. (replicas summed)
+  int lab;
+  float2 ptv;     // P^T row tid>>5, images 2*(tid&31)..
+  float4 xv;      // threads < 256: row tid&3 of the 4x4 patch of image tid>>2
+  uint64_t amv;   // threads < 256: argmax bytes of channel group tid>>6, image tid&63
+};
+
+// Issues every global load of the chunk before anything waits: straight-line, with indices clamped
+// into the chunk (rows past nb read row nb-1, replicas past hrep read replica hrep-1 — never an address
+// outside the buffers) and the values of the clamped lanes replaced afterwards.  NREP = replica slots
+// (0: the runtime loop of the deterministic mode, after the other loads are in flight).
+template <int NREP>
+__device__ __forceinline__ void bwd32_chunk_issue(const BwdArgs& a, int tid, int p, int py, int px, int b0, int nb,
+                                                  Bwd32Chunk& c) {
+  const int last = nb - 1;
+  const int hrow = b0 + min(tid >> 4, last), hc4 = (tid & 15) * 4;
+  HpreRep<(NREP > 0 ? NREP : 1)> h;
+  if (NREP > 0) h.issue(a, hrow, hc4);
+  c.lab = a.labels[b0 + min(tid, last)];
+  // the pair starts at an even column <= nb-1; ldPt is even and >= B, so its second float is in the row
+  const int pc = (tid & 31) * 2;
+  c.ptv = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(a.Pt) + (size_t)(p * CC + (tid >> 5)) * a.ldPt +
+                                           b0 + min(pc, last & ~1));
+  c.xv = float4{0.f, 0.f, 0.f, 0.f};
+  c.amv = ~0ull;
+  if (tid < 256) {
+    const int bl = tid >> 2, r = tid & 3;
+    const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + min(bl, last)) * a.H * a.W +
+                                                        (2 * py + r) * a.W + 2 * px);
+    const float2 u = row[0], t = row[1];
+    c.xv = float4{u.x, u.y, t.x, t.y};
+    const int cg = tid >> 6, bb = tid & 63;
+    c.amv = a.amax[((size_t)p * (CC / 8) + cg) * a.lda + b0 + min(bb, last)];
+  }
+  c.hv = NREP > 0 ? h.sum(a) : load_hpre_loop(a, hrow, hc4);   // rows past nb: zeroed by head_stage
+  if ((tid >> 2) >= nb) c.xv = float4{0.f, 0.f, 0.f, 0.f};
+  if ((tid & 63) >= nb) c.amv = ~0ull;
+  if (tid >= nb) c.lab = 0;
+  if (pc >= nb) c.ptv.x = 0.f;
+  if (pc + 1 >= nb) c.ptv.y = 0.f;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -198,52 +280,53 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   uint8_t* am = smem + kAm32;
   float* dps = reinterpret_cast<float*>(smem + kR32);
   const HeadLds hl = HeadLds::carve(smem + kR32, smem + kW2s32, smem + kB2s32, smem + kLab32);
+  // MODE 2: the step count, read before the kernel's first store (a scalar load, used only by the epilogue:
+  // nothing waits for it here); MODE 1 (SGD) does not read it in the trunk workgroups
+  long long t_it = 0;
+  if (MODE == 2) t_it = *a.iterations;
+  const unsigned nwg = gridDim.x;   // read once, ahead of the first branch (a scalar load)
   stamp(a.stamps, 0);
-  const int W = a.W, H = a.H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
-  const int fr = lane & 15, fq = lane >> 4;
+  const int W = a.W;
+  int tid, lane, wave, fr, fq;
+  bwd32_ids(tid, lane, wave, fr, fq);
   const float* W1 = reinterpret_cast<const float*>(a.W1);
-  const float* Pt = reinterpret_cast<const float*>(a.Pt);
 
   // the head weights into registers now, stored to LDS with the chunk operands below: every global load
-  // of the prologue is in flight before the first LDS store (one round trip, not three)
-  const int u2 = tid >> 4, c2 = tid & 15;   // 64 x 16
-  const float w2v = c2 < a.C ? a.W2[u2 * a.C + c2] : 0.f;
-  const float b2v = (tid < 16 && tid < a.C) ? a.b2[tid] : 0.f;
+  // of the prologue is in flight before the first LDS store (one round trip, not three).  Straight-line:
+  // classes past C read class C-1 and store 0.
+  float w2v, b2v;
+  {
+    const int u2 = tid >> 4, c2 = tid & 15;   // 64 x 16
+    w2v = a.W2[u2 * a.C + min(c2, a.C - 1)];
+    b2v = a.b2[min(c2, a.C - 1)];
+  }
   zero_other_parity(a, tid);
-  if (blockIdx.x == gridDim.x - 1) {
-    hl.w2s[u2 * W2S + c2] = w2v;
-    if (tid < 16) hl.b2s[tid] = b2v;
-    head_workgroup<MODE>(a, hl, Gs);   // the G area is unused there
+  if (blockIdx.x == nwg - 1) {
+    hl.w2s[(tid >> 4) * W2S + (tid & 15)] = (tid & 15) < a.C ? w2v : 0.f;
+    if (tid < 16) hl.b2s[tid] = tid < a.C ? b2v : 0.f;
+    head_workgroup<MODE, true>(a, hl, Gs);   // the G area is unused there
     return;
   }
 
   const int Wp = (W - 2) / 2;
   const int p = blockIdx.x;            // one pooled position per workgroup (grid = P + 1)
   const int py = p / Wp, px = p - py * Wp;
-  const int hr = tid >> 4, hc4 = (tid & 15) * 4;
-  const float4 b1v = a.b1 ? *reinterpret_cast<const float4*>(a.b1 + hc4) : float4{0.f, 0.f, 0.f, 0.f};
+  // no Dense(64) bias: the load reads hpre's first row (same alignment) and counts as 0
+  const float4 b1v = *reinterpret_cast<const float4*>((a.b1 ? a.b1 : a.hpre) + (tid & 15) * 4);
   // roles: waves 0-7 dP tile (mt = wave>>1 images, ct = wave&1 channels);
   //        waves 8-15 dW1 tile (rt = v>>2 channels, nt = v&3 units), v = wave-8
-  const bool dw_wave = wave >= 8;
-  const int v8 = wave & 7;
-
   f32x4 accw = {0.f, 0.f, 0.f, 0.f};
   f32x4 accr[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 
   // fused step with slots: the dW1-wave's slot values, loaded now (the weights come from W1s)
   f32x4 mp = {0.f, 0.f, 0.f, 0.f}, vp = {0.f, 0.f, 0.f, 0.f};
-  long long t_it = 0;
-  if (MODE != 0) {
-    t_it = *a.iterations;
-    if (MODE == 2 && dw_wave) {
-      const int rt = v8 >> 2, nt = v8 & 3;
+  if (MODE == 2 && wave >= 8) {
+    const int rt = (wave & 7) >> 2, nt = wave & 3;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const size_t e = (size_t)(p * CC + rt * 16 + fq * 4 + r) * HD + nt * 16 + fr;
-        if (a.h.kind != kOptSGD) mp[r] = a.m1[e];
-        if (a.h.kind == kOptAdam) vp[r] = a.v1[e];
-      }
+    for (int r = 0; r < 4; ++r) {
+      const size_t e = (size_t)(p * CC + rt * 16 + fq * 4 + r) * HD + nt * 16 + fr;
+      if (a.h.kind != kOptSGD) mp[r] = a.m1[e];
+      if (a.h.kind == kOptAdam) vp[r] = a.v1[e];
     }
   }
 
@@ -253,46 +336,37 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
 
   for (int b0 = 0; b0 < a.B; b0 += 64) {
     const int nb = min(64, a.B - b0);
-    // ---- prologue: coalesced loads of this chunk's operands
-    float4 hv = {0.f, 0.f, 0.f, 0.f};
-    if (hr < nb) hv = load_hpre(a, b0 + hr, hc4);
-    const int lab = (tid < nb) ? a.labels[b0 + tid] : 0;
-    float2 ptv;
-    {
-      const int r = tid >> 5, c = (tid & 31) * 2;
-      const float* src = Pt + (size_t)(p * CC + r) * a.ldPt + b0 + c;
-      ptv.x = c < nb ? src[0] : 0.f;
-      ptv.y = c + 1 < nb ? src[1] : 0.f;
-    }
-    float4 xv = {0.f, 0.f, 0.f, 0.f};
-    uint64_t amv = ~0ull;
-    if (tid < 256) {
-      const int bl = tid >> 2, r = tid & 3;
-      if (bl < nb) {
-        const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + bl) * H * W + (2 * py + r) * W + 2 * px);
-        const float2 u = row[0], t = row[1];
-        xv = float4{u.x, u.y, t.x, t.y};
-      }
-      const int cg = tid >> 6, bb = tid & 63;
-      if (bb < nb) amv = a.amax[((size_t)p * (CC / 8) + cg) * a.lda + b0 + bb];
+    bwd32_ids(tid, lane, wave, fr, fq);
+    const bool dw_wave = wave >= 8;
+    const int v8 = wave & 7;
+    // ---- prologue: this chunk's operands, every load issued before the first wait; the replica count
+    // picks the number of hpre registers (uniform switch; more than kMaxRep: the deterministic mode)
+    Bwd32Chunk ck;
+    if (a.hrep > kMaxRep) bwd32_chunk_issue<0>(a, tid, p, py, px, b0, nb, ck);
+    else switch (a.hrep) {
+      case 1: bwd32_chunk_issue<1>(a, tid, p, py, px, b0, nb, ck); break;
+      case 2: bwd32_chunk_issue<2>(a, tid, p, py, px, b0, nb, ck); break;
+      case 3: case 4: bwd32_chunk_issue<4>(a, tid, p, py, px, b0, nb, ck); break;
+      default: bwd32_chunk_issue<8>(a, tid, p, py, px, b0, nb, ck); break;
     }
     stamp(a.stamps, 1);
+    // the selects of the clamped chunk-0 loads use this iteration's thread indices: they stay here, behind
+    // the chunk's loads, and are not moved up to the loads they would wait for (has_b1: always a.b1 != null)
+    const bool has_b1 = a.b1 && tid >= 0;
+    const float4 b1u = has_b1 ? b1v : float4{0.f, 0.f, 0.f, 0.f};
     if (b0 == 0) {
-      hl.w2s[u2 * W2S + c2] = w2v;
-      if (tid < 16) hl.b2s[tid] = b2v;
+      hl.w2s[(tid >> 4) * W2S + (tid & 15)] = (tid & 15) < a.C ? w2v : 0.f;
+      if (tid < 16) hl.b2s[tid] = tid < a.C ? b2v : 0.f;
       *reinterpret_cast<float2*>(W1s + (tid >> 5) * GS32 + (tid & 31) * 2) = w1v;
     }
-    head_stage(a, hv, b1v, hr, hc4, nb, hl.hs);
-    if (tid < 64) hl.labs[tid] = lab;
-    {
-      const int r = tid >> 5, c = (tid & 31) * 2;
-      *reinterpret_cast<float2*>(Pts + r * GS32 + c) = ptv;
-    }
+    head_stage(a, ck.hv, b1u, tid >> 4, (tid & 15) * 4, nb, hl.hs);
+    if (tid < 64) hl.labs[tid] = ck.lab;
+    *reinterpret_cast<float2*>(Pts + (tid >> 5) * GS32 + (tid & 31) * 2) = ck.ptv;
     if (tid < 256) {
       const int bl = tid >> 2, r = tid & 3;
-      *reinterpret_cast<float4*>(xs + bl * 16 + r * 4) = xv;
+      *reinterpret_cast<float4*>(xs + bl * 16 + r * 4) = ck.xv;
       const int cg = tid >> 6, bb = tid & 63;
-      *reinterpret_cast<uint64_t*>(am + bb * CC + cg * 8) = amv;
+      *reinterpret_cast<uint64_t*>(am + bb * CC + cg * 8) = ck.amv;
     }
     lds_barrier();
     // ---- the head recomputed: G = dH (f32) into LDS, row-major and transposed
@@ -352,6 +426,9 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   }
   stamp(a.stamps, 4);
 
+  bwd32_ids(tid, lane, wave, fr, fq);
+  const bool dw_wave = wave >= 8;
+  const int v8 = wave & 7;
   if (dw_wave) {
     const int rt = v8 >> 2, nt = v8 & 3;
     const int col = nt * 16 + fr;
