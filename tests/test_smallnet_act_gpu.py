@@ -1,12 +1,13 @@
 """tanh / sigmoid activations and AveragePooling2D(2) in the fused small-net plan (csrc/kernels/smallnet.hip,
-train/smallnet.py) against the float64 oracle of tests/smallnet_act_oracle.py.
+train/smallnet.py) against the float64 oracle of tests/smallnet_oracle.py on the act suite of
+tests/smallnet_cases.py.
 
 Per (model, batch), step mode "plain": every variable's gradient, the loss sum, the eval loss and predict
 norm-wise relative to float64, bound = max(1e-5, 4 x the error of the fp32 torch CPU reference plan against
 the same oracle, computed on the spot); correct count, image count and ``iterations`` exact.  The new
 operations are smooth, so data is unquantized randn; the decisions that remain (ReLU signs, max-pool argmax
 behind a tanh conv, the head's argmax) are required to be 1e-4 rms away from a tie on the oracle
-(smallnet_act_oracle: relu_near, pool_gap, margin; seeds committed there).
+(smallnet_oracle: relu_near, pool_gap, margin; seeds committed in smallnet_cases).
 
 What each model reaches (codes: 0 linear, 1 relu, 2 tanh, 3 sigmoid; sn_act = forward helper, sn_act_bwd =
 derivative from the stored output, applied where a gradient overwrites that output):
@@ -40,7 +41,7 @@ dgrad_tanh, input 18x18x1, B = 37 in a plan of 64: Conv2D(6, 5, tanh) . Conv2D(1
   pool in between: the compile-time input-gradient forms with a derivative code, mask_in = 2
   mask 3 (default), mask 0    sn_conv_dgrad_c<4> multiplies by 1 - y^2 as it overwrites conv 1's output
   mask 7 (child)              sn_conv_dgrad_m does
-Masks 0 and 7 run in one fresh child process each (tests/_smallnet_act_child.py): the library reads
+Masks 0 and 7 run in one fresh child process each (tests/_smallnet_child.py act): the library reads
 TDE_SN_MFMA once per process.  The children's conv-gradient hashes must differ from the in-process ones
 where the mask changes the summation order, otherwise a child tested the default forms.
 
@@ -66,69 +67,33 @@ average pool).  A second one -- sn_conv_dgrad_c and sn_conv_dgrad_m writing the 
 derivative factor -- fails dgrad_tanh in-process and in both children (conv2d/kernel at 0.358 each) and
 nothing else.
 """
-import json
 import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-import smallnet_act_oracle as A
+import smallnet_cases as C
+import smallnet_oracle as O
+from smallnet_child import guard, run
 
 pytestmark = pytest.mark.gpu
-REPO = Path(__file__).resolve().parents[1]
-CHILD_TIMEOUT = 120     # s: a cold import of torch, loading the code objects, one plan and its CPU oracle
-
-_CRASHED = []           # set when a child ends by signal or at its time limit: no GPU work after that
-_CHILDREN = {}
-
-
-def _guard():
-    if _CRASHED:
-        pytest.fail(f"not run: {_CRASHED[0]}")
-
-
-def _child(mask):
-    if mask in _CHILDREN:
-        return _CHILDREN[mask]
-    _guard()
-    env = dict(os.environ, PYTHONPATH=str(REPO), TDE_SN_MFMA=mask)
-    try:
-        p = subprocess.run([sys.executable, str(REPO / "tests" / "_smallnet_act_child.py")], env=env,
-                           capture_output=True, text=True, timeout=CHILD_TIMEOUT, cwd=str(REPO))
-    except subprocess.TimeoutExpired as e:
-        _CRASHED.append(f"the TDE_SN_MFMA={mask} child hit its {CHILD_TIMEOUT} s limit")
-        pytest.fail(f"{_CRASHED[0]}\n{e.stdout}\n{e.stderr}")
-    if p.returncode < 0:
-        _CRASHED.append(f"the TDE_SN_MFMA={mask} child ended by signal {-p.returncode}")
-        pytest.fail(f"{_CRASHED[0]}\n{p.stdout}\n{p.stderr}")
-    assert p.returncode == 0, p.stdout + p.stderr
-    lines = [l for l in p.stdout.splitlines() if l.startswith("SMALLNET_ACT ")]
-    assert len(lines) == 1, p.stdout + p.stderr
-    out = json.loads(lines[0][len("SMALLNET_ACT "):])
-    assert out["mask"] == mask
-    _CHILDREN[mask] = out
-    return out
-
 
 _DEFAULT = {}
 
 
 def _default_fig(tde, name, B, Bplan):
     if (name, B) not in _DEFAULT:
-        _DEFAULT[name, B] = A.measure(tde, name, B, Bplan)
+        _DEFAULT[name, B] = O.measure(tde, "act", name, B, Bplan)
     return _DEFAULT[name, B]
 
 
-@pytest.mark.parametrize("name,B,Bplan", A.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["act"])
 def test_act_default_mask(name, B, Bplan):
     """Every model and batch in-process (TDE_SN_MFMA default 3)."""
     import tensorflow_distributed_example_amd as tde
-    _guard()
-    A.check(_default_fig(tde, name, B, Bplan))
+    guard()
+    O.check(_default_fig(tde, name, B, Bplan))
 
 
 @pytest.mark.parametrize("mask", ["0", "7"])
@@ -138,13 +103,13 @@ def test_act_child_mask(mask):
     conv 2's input gradient, so conv 1's kernel gradient (downstream of it) differs in bits and conv 2's
     (same MFMA forms on the same operands) does not."""
     import tensorflow_distributed_example_amd as tde
-    out = _child(mask)
-    assert [f["name"] for f in out["figs"]] == list(A.FAST)
+    out = run("act", mask)
+    assert [(f["suite"], f["name"], f["data"]) for f in out["figs"]] == [("act", n, "randn") for n in C.FAST["act"]]
     for fig in out["figs"]:
-        A.check(fig)
-    _guard()
+        O.check(fig)
+    guard()
     assert os.environ.get("TDE_SN_MFMA", "3") == "3", "the in-process side of this test is the default mask"
-    h3 = _default_fig(tde, "lenet5_classic", *A.O.FAST_BATCH)["conv_grad_hash"]
+    h3 = _default_fig(tde, "lenet5_classic", *C.FAST_BATCH)["conv_grad_hash"]
     h = out["figs"][0]["conv_grad_hash"]
     c1, c2 = sorted(h3)          # conv2d/kernel, conv2d_1/kernel
     assert sorted(h) == [c1, c2]
@@ -170,7 +135,7 @@ def test_act_local_step_matches_plain(opt):
     at test_smallnet_local_step_matches_plain's bound."""
     import tensorflow_distributed_example_amd as tde
     from tensorflow_distributed_example_amd.train import program as PG
-    _guard()
+    guard()
 
     def mk():
         return {"momentum": tde.optimizers.SGD(0.05, momentum=0.9), "adam": tde.optimizers.Adam(1e-3)}[opt]
@@ -204,7 +169,7 @@ def test_act_fit_lenet5_classic():
     """fit() on the classic LeNet-5 picks the fused small-net plan and learns the separable synthetic task of
     test_smallnet_fit_lenet5 (same data, optimizer and loss criterion)."""
     import tensorflow_distributed_example_amd as tde
-    _guard()
+    guard()
     tde.backend.set_random_seed(4)
     m = tde.zoo.lenet5_classic()
     m.compile(loss=tde.losses.SparseCategoricalCrossentropy(from_logits=True), optimizer=tde.optimizers.SGD(0.05),
@@ -227,7 +192,7 @@ def test_refused_model_keeps_todays_error():
     ``NotImplementedError`` as before."""
     import tensorflow_distributed_example_amd as tde
     from tensorflow_distributed_example_amd.train import program as PG
-    _guard()
+    guard()
     K = tde.keras.layers
     m = tde.Sequential([K.Dense(8, activation="tanh", input_shape=(6,)), K.Dropout(0.5), K.Dense(3)])
     m.compile(loss=tde.losses.SparseCategoricalCrossentropy(from_logits=True), optimizer=tde.optimizers.SGD(0.01))
@@ -241,8 +206,8 @@ def test_unknown_codes_are_refused():
     import tensorflow_distributed_example_amd as tde
     from tensorflow_distributed_example_amd.train import program as PG
     from tensorflow_distributed_example_amd.train import smallnet as SN
-    _guard()
-    m, x, y = A.make_case(tde, "mlp_tanh", 5, 8)
+    guard()
+    m, x, y = C.make_case(tde, "act", "mlp_tanh", 5, 8)
     plan = PG.make_plan(m, m._store, "cuda", 8, 8, m.optimizer, m.loss)
     col = {f: i for i, f in enumerate(SN._FIELDS)}
     good = plan.layers.copy()

@@ -1,6 +1,7 @@
 """tanh / sigmoid / AveragePooling2D on the fused small-net plan, the parts that need no GPU: the float64
-oracle of tests/smallnet_act_oracle.py against the repository's fp32 ``ReferencePlan`` on the CPU for every
-model and batch of tests/test_smallnet_act_gpu.py, the input conditions at the committed seeds, what
+oracle of tests/smallnet_oracle.py against the repository's fp32 ``ReferencePlan`` on the CPU for every model
+and batch of tests/test_smallnet_act_gpu.py (the act suite of tests/smallnet_cases.py), the input conditions at
+the committed seeds, what
 ``match_smallnet`` accepts and refuses, the plan table's kinds and activation codes, the
 ``AveragePooling2D`` layer itself and its ``AvgPool`` / ``Tanh`` export.
 
@@ -15,30 +16,31 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import smallnet_act_oracle as A
+import smallnet_cases as C
+import smallnet_oracle as O
 
 
 def _logits(tde):
     return tde.losses.SparseCategoricalCrossentropy(from_logits=True)
 
 
-@pytest.mark.parametrize("name,B,Bplan", A.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["act"])
 def test_oracle_matches_fp32_reference(name, B, Bplan):
     import tensorflow_distributed_example_amd as tde
-    m, x, y = A.make_case(tde, name, B, Bplan)
-    orc = A.oracle(m, m._store, x, y, B, Bplan)
-    ref = A.O.reference_errors(tde, m, x, y, B, Bplan, orc)
+    m, x, y = C.make_case(tde, "act", name, B, Bplan)
+    orc = O.oracle(m, m._store, x, y, B, Bplan)
+    ref = O.reference_errors(tde, m, x, y, B, Bplan, orc)
     tag = f"{name} B={B}/{Bplan}"
     print(f"[{tag}] relu_near={orc['relu_near']:.3g} pool_gap={orc['pool_gap']:.3g} margin={orc['margin']:.3g} "
           f"loss={ref['loss']:.2g} predict={ref['predict']:.2g}")
     for n, e in ref["grads"].items():
         print(f"[{tag}] grad {n}: {e:.2g}")
-    assert A.conditions_hold(orc), (orc["relu_near"], orc["pool_gap"], orc["margin"])
+    assert O.conditions_hold(orc), (orc["relu_near"], orc["pool_gap"], orc["margin"])
     assert all(torch.isfinite(g).all() and g.abs().max() > 0 for g in orc["grads"].values())
     assert set(orc["grads"]) == set(m._store.names(trainable=True))
     for n, e in ref["grads"].items():
-        assert e < A.TOL, (n, e)
-    assert ref["loss"] < A.TOL and ref["eval_loss"] < A.TOL and ref["predict"] < A.TOL
+        assert e < O.TOL, (n, e)
+    assert ref["loss"] < O.TOL and ref["eval_loss"] < O.TOL and ref["predict"] < O.TOL
     assert ref["correct"] == ref["eval_correct"] == orc["correct"] and ref["count"] == B
     assert orc["out"].shape == (B, m.output_shape[-1])
 
@@ -46,16 +48,16 @@ def test_oracle_matches_fp32_reference(name, B, Bplan):
 def test_conditions_measure_what_they_name():
     """A ReLU at zero, a tied max-pool window behind a tanh conv and a tied head are each seen."""
     h = torch.tensor([[[[0.5], [0.5]], [[0.1], [0.2]]]], dtype=torch.float64)       # one 2x2 window, two maxima
-    assert A._window_gap(h) == 0.0
+    assert O._window_gap(h) == 0.0
     h[0, 0, 1, 0] = 0.25
-    assert A._window_gap(h) == pytest.approx(0.25 / h.pow(2).mean().sqrt().item())
+    assert O._window_gap(h) == pytest.approx(0.25 / h.pow(2).mean().sqrt().item())
     odd = torch.zeros(1, 3, 3, 1, dtype=torch.float64)      # the odd row / column belongs to no window
     odd[0, :2, :2, 0] = torch.tensor([[1.0, 0.0], [0.0, 0.0]])
     odd[0, 2, :, 0] = 1.0
-    assert A._window_gap(odd) > 0
+    assert O._window_gap(odd) > 0
 
 
-@pytest.mark.parametrize("name", list(A.MODELS))
+@pytest.mark.parametrize("name", list(C.MODELS["act"]))
 def test_matcher_and_plan_codes(name):
     """``match_smallnet`` accepts every model with the expected entry kinds and activation codes, no other
     fused plan's matcher takes it first, and the plan table carries the codes: ``act`` the entry's own,
@@ -65,8 +67,8 @@ def test_matcher_and_plan_codes(name):
     from tensorflow_distributed_example_amd.train import smallnet as SN
     assert (SN.CONV, SN.POOL, SN.DENSE, SN.AVGPOOL) == (0, 1, 2, 3)
     assert (SN.LINEAR, SN.RELU, SN.TANH, SN.SIGMOID) == (0, 1, 2, 3)
-    m, _ = A.build(tde, name, 5)
-    kinds, codes, mask_in = A.MODELS[name][2:]
+    m, _ = C.build(tde, "act", name, 5)
+    kinds, codes, mask_in = C.MODELS["act"][name].codes
     assert PG.match_convnet(m, m.loss) is None
     spec = SN.match_smallnet(m, m.loss)
     assert spec is not None
@@ -196,7 +198,7 @@ def test_lenet5_classic_saved_model(tmp_path):
     m = tde.zoo.lenet5_classic()
     m.compile(loss=_logits(tde), optimizer=tde.optimizers.SGD(0.01))
     m.build()
-    m._store.load_dict(A.O.make_weights(m, np.random.default_rng(5), None), strict=True)
+    m._store.load_dict(O.make_weights(m, np.random.default_rng(5), None), strict=True)
     path = EX.export_saved_model(m, str(tmp_path / "exp"), lambda: EX.TensorServingInputReceiver(
         EX.placeholder("float32", [None, 28, 28, 1]), {}))
     path = path.decode() if isinstance(path, bytes) else path

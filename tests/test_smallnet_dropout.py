@@ -1,11 +1,12 @@
 """CPU side of Dropout on the fused small-net plan: the matcher, the shared seed / layer-id helper
 against what the layer-wise plan holds, and the float64 oracle's mask plumbing and input conditions
-(tests/smallnet_dropout_oracle.py).  The kernels themselves: tests/test_smallnet_dropout_gpu.py."""
+(tests/smallnet_oracle.py on the dropout suite of tests/smallnet_cases.py).  The kernels themselves:
+tests/test_smallnet_dropout_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
-import smallnet_dropout_oracle as D
+import smallnet_cases as C
 import smallnet_oracle as O
 
 
@@ -27,16 +28,16 @@ def test_matcher_accepts_dropout_with_the_right_owner():
     from tensorflow_distributed_example_amd.train.smallnet import CONV, DENSE, POOL, match_smallnet
     tde, K = _tde()
     for name in ("mask_probe", "pool_drop", "conv_drop", "linear_drop", "linear_rate0", "lenet5_drop"):
-        m, _, _ = D.make_case(tde, name, 5, 8)
+        m, _, _ = C.make_case(tde, "dropout", name, 5, 8)
         spec = match_smallnet(m, m.loss)
         assert spec is not None, name
         drops = [l.name for l in m.layers if isinstance(l, L.Dropout)]
         assert [o for o in _owners(spec) if o] == drops, name
-    m, _, _ = D.make_case(tde, "pool_drop", 5, 8)
+    m, _, _ = C.make_case(tde, "dropout", "pool_drop", 5, 8)
     spec = match_smallnet(m, m.loss)
     assert [s["kind"] for s in spec] == [CONV, POOL, DENSE, DENSE]
     assert [o is not None for o in _owners(spec)] == [False, True, True, False]
-    m, _, _ = D.make_case(tde, "conv_drop", 5, 8)
+    m, _, _ = C.make_case(tde, "dropout", "conv_drop", 5, 8)
     assert [o is not None for o in _owners(match_smallnet(m, m.loss))] == [True, False, False]
     # a Flatten and a standalone ReLU between the owner and its Dropout
     m = tde.Sequential([K.Conv2D(4, 3, input_shape=(6, 6, 2)), K.Activation("relu"), K.Flatten(), K.Dropout(0.3),
@@ -97,11 +98,11 @@ def test_seed_and_lid_helper_matches_layerwise_plan(which):
     tde.backend.set_global_policy("float32")
     try:
         want_lids = None
-        if which in D.MODELS:
-            m, _, _ = D.make_case(tde, which, 5, 8)
+        if which in C.MODELS["dropout"]:
+            m, _, _ = C.make_case(tde, "dropout", which, 5, 8)
             want_lids = {"pool_drop": [0, 1], "conv_drop": [0], "linear_drop": [0], "lenet5_drop": [0, 1]}[which]
         else:
-            tde.backend.set_random_seed(D.MODEL_SEED)
+            tde.backend.set_random_seed(C.MODEL_SEED)
             m, want_lids = _act_models(tde, K)[which]
             m.compile(loss=_logits(tde), optimizer=tde.optimizers.SGD(0.01))
             m.build()
@@ -130,13 +131,13 @@ def test_oracle_mask_plumbing(step):
     tde, _ = _tde()
     B = 7
     for name in ("mask_probe", "pool_drop"):
-        m, x, y = D.make_case(tde, name, B, 8)
+        m, x, y = C.make_case(tde, "dropout", name, B, 8)
         first = m.layers[0] if m.layers[0].weight_specs else m.layers[1]
         st = m._store
         st.view(f"{first.name}/kernel").zero_()
         st.view(f"{first.name}/bias").fill_(1.0)
-        orc = D.oracle(m, st, x, y, B, 8, step)
-        tab = D.drop_table(m)
+        orc = O.oracle(m, st, x, y, B, 8, step)
+        tab = O.drop_table(m)
         dname = [n for n in tab][0]
         rate, seed, lid = tab[dname]
         got = orc["dropped"][dname]
@@ -147,22 +148,22 @@ def test_oracle_mask_plumbing(step):
         assert 0 < (want == 0).mean() < 1
         if name == "mask_probe":
             assert (rate, seed, lid) == (0.5, 1234, 0)
-        none = D.oracle(m, st, x, y, B, 8, None)["dropped"][dname]
+        none = O.oracle(m, st, x, y, B, 8, None)["dropped"][dname]
         assert torch.equal(none, torch.ones_like(none))
 
 
-@pytest.mark.parametrize("name,B,Bplan", D.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["dropout"])
 def test_conditions_hold_and_fp32_reference_is_close(name, B, Bplan):
     """The input conditions the GPU tests rest on (exact conv trunk, headroom, near-tie, margin), and the
     fp32 CPU evaluation of the oracle (the reference whose error sets the GPU bound) against float64."""
     tde, _ = _tde()
-    c = D.conditions(tde, name, B, Bplan)
+    c = O.conditions(tde, name, B, Bplan)
     print(f"[{name} B={B}/{Bplan}] {c}")
-    assert c["exact"] and c["headroom"] > 1.0
+    assert c["trunk_exact"] and c["headroom"] > 1.0
     assert c["near_tie"] > O.TIE and c["margin"] > O.TIE
-    m, x, y = D.make_case(tde, name, B, Bplan)
-    o64 = D.oracle(m, m._store, x, y, B, Bplan, 0)
-    o32 = D.oracle(m, m._store, x, y, B, Bplan, 0, dtype=torch.float32)
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
+    o64 = O.oracle(m, m._store, x, y, B, Bplan, 0)
+    o32 = O.oracle(m, m._store, x, y, B, Bplan, 0, dtype=torch.float32)
     assert set(o64["grads"]) == set(m._store.names(trainable=True))
     for n, g in o64["grads"].items():
         e = O.rel(o32["grads"][n], g)
@@ -170,16 +171,16 @@ def test_conditions_hold_and_fp32_reference_is_close(name, B, Bplan):
         assert torch.isfinite(g).all() and g.abs().max() > 0 and e < O.TOL, (n, e)
     assert o32["correct"] == o64["correct"]
     # the masks matter: another step index gives other gradients
-    o1 = D.oracle(m, m._store, x, y, B, Bplan, 1)
+    o1 = O.oracle(m, m._store, x, y, B, Bplan, 1)
     assert any(O.rel(o1["grads"][n], g) > 1e-2 for n, g in o64["grads"].items())
 
 
 def test_trajectory_conditions():
     """Near-tie and margin along the three SGD steps of the trajectory test, on the oracle alone."""
     tde, _ = _tde()
-    name, B, Bplan = D.TRAJ
-    m, x, y = D.make_case(tde, name, B, Bplan)
-    _, figs = D.trajectory(m, m._store, x, y, B, Bplan, 0.01, D.TRAJ_STEPS)
+    name, B, Bplan = C.TRAJ
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
+    _, figs = O.trajectory(m, m._store, x, y, B, Bplan, 0.01, C.TRAJ_STEPS)
     for k, f in enumerate(figs):
         print(f"[traj step {k}] near_tie={f['near_tie']:.3g} margin={f['margin']:.3g}")
         assert f["near_tie"] > O.TIE and f["margin"] > O.TIE

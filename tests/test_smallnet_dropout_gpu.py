@@ -3,8 +3,8 @@
 The mask is observed directly (an all-ones activation times the keep scale lands in the head's input
 record) at step indices 0, 1 and a restored 41, at a batch of more workgroups than fit on the device at
 once -- where a step index read from ``iterations`` by late workgroups would show as rows drawn from
-step + 1.  Gradients, loss and counts are compared with the float64 oracle of
-tests/smallnet_dropout_oracle.py under the project's bound, max(1e-5, 4 x the error of the same oracle
+step + 1.  Gradients, loss and counts are compared with the float64 oracle of tests/smallnet_oracle.py on
+the dropout suite of tests/smallnet_cases.py under the project's bound, max(1e-5, 4 x the error of the same oracle
 in torch fp32 on the CPU with the same masks); the conditions on the inputs (exact conv trunk, near-tie,
 margin) are asserted on the CPU in tests/test_smallnet_dropout.py.
 
@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-import smallnet_dropout_oracle as D
+import smallnet_cases as C
 import smallnet_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -60,7 +60,7 @@ def test_mask_observed_directly(batch):
         B, Bplan = 5, 8
     else:
         B = Bplan = 2 * torch.cuda.get_device_properties(0).multi_processor_count + 37
-    m, _, _ = D.make_case(tde, "mask_probe", B, Bplan)
+    m, _, _ = C.make_case(tde, "dropout", "mask_probe", B, Bplan)
     st = m._store
     first = [l for l in m.layers if l.weight_specs][0]
     st.view(f"{first.name}/kernel").zero_()
@@ -94,15 +94,15 @@ def test_mask_observed_directly(batch):
     step_and_check(42, 43)
 
 
-@pytest.mark.parametrize("name,B,Bplan", D.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["dropout"])
 def test_gradients_loss_and_counts_match_oracle(name, B, Bplan):
     tde, PG = _tde()
-    m, x, y = D.make_case(tde, name, B, Bplan)
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
     st = m._store
-    orc = D.oracle(m, st, x, y, B, Bplan, 0)
-    o32 = D.oracle(m, st, x, y, B, Bplan, 0, dtype=torch.float32)
+    orc = O.oracle(m, st, x, y, B, Bplan, 0)
+    o32 = O.oracle(m, st, x, y, B, Bplan, 0, dtype=torch.float32)
     plan = _plan(PG, m, Bplan)
-    assert len(plan.drops) == sum(r > 0 for r, _, _ in D.drop_table(m).values())
+    assert len(plan.drops) == sum(r > 0 for r, _, _ in O.drop_table(m).values())
     plan.train_step(x.cuda(), y.cuda(), B)
     torch.cuda.synchronize()
     tag = f"{name} B={B}/{Bplan}"
@@ -118,8 +118,8 @@ def test_gradients_loss_and_counts_match_oracle(name, B, Bplan):
 def test_eval_and_predict_are_mask_free():
     tde, PG = _tde()
     name, (B, Bplan) = "pool_drop", (5, 8)
-    m, x, y = D.make_case(tde, name, B, Bplan)
-    orc = D.oracle(m, m._store, x, y, B, Bplan, None)
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
+    orc = O.oracle(m, m._store, x, y, B, Bplan, None)
     plan = _plan(PG, m, Bplan)
     xg, yg = x.cuda(), y.cuda()
     plan.train_step(xg, yg, B)
@@ -134,31 +134,31 @@ def test_eval_and_predict_are_mask_free():
     assert me[1].item() == orc["correct"] and me[2].item() == B and tuple(p.shape) == (B, 5)
     assert plan.iterations.item() == 1
     # and the masked loss is another number: eval really ran without the masks
-    masked = D.oracle(m, m._store, x, y, B, Bplan, 1)["loss"]
+    masked = O.oracle(m, m._store, x, y, B, Bplan, 1)["loss"]
     assert abs(masked - orc["loss"]) / abs(orc["loss"]) > 1e-3
 
 
 def test_three_local_sgd_steps_follow_the_masks_of_steps_0_1_2():
     tde, PG = _tde()
-    name, B, Bplan = D.TRAJ
-    m, x, y = D.make_case(tde, name, B, Bplan)
+    name, B, Bplan = C.TRAJ
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
     st = m._store
     lr = float(m.optimizer.learning_rate)
     w0 = {n: st.view(n).detach().cpu().double().clone() for n in st.names(trainable=True)}
-    w64, figs = D.trajectory(m, st, x, y, B, Bplan, lr, D.TRAJ_STEPS)
-    w32, _ = D.trajectory(m, st, x, y, B, Bplan, lr, D.TRAJ_STEPS, dtype=torch.float32)
-    frozen, _ = D.trajectory(m, st, x, y, B, Bplan, lr, D.TRAJ_STEPS, mask_steps=[0] * D.TRAJ_STEPS)
+    w64, figs = O.trajectory(m, st, x, y, B, Bplan, lr, C.TRAJ_STEPS)
+    w32, _ = O.trajectory(m, st, x, y, B, Bplan, lr, C.TRAJ_STEPS, dtype=torch.float32)
+    frozen, _ = O.trajectory(m, st, x, y, B, Bplan, lr, C.TRAJ_STEPS, mask_steps=[0] * C.TRAJ_STEPS)
     # the step-1 gradient with the step-0 mask is another gradient (oracle alone, at the step-1 weights)
-    w1, _ = D.trajectory(m, st, x, y, B, Bplan, lr, 1)
-    g_same = D.oracle(m, st, x, y, B, Bplan, 0, weights=w1)["grads"]
+    w1, _ = O.trajectory(m, st, x, y, B, Bplan, lr, 1)
+    g_same = O.oracle(m, st, x, y, B, Bplan, 0, weights=w1)["grads"]
     assert any(O.rel(g_same[n], figs[1]["grads"][n]) > 1e-2 for n in g_same)
     plan = _plan(PG, m, Bplan)
     plan.set_step_mode("local")
     xg, yg = x.cuda(), y.cuda()
-    for _ in range(D.TRAJ_STEPS):
+    for _ in range(C.TRAJ_STEPS):
         plan.train_step(xg, yg, B)
     torch.cuda.synchronize()
-    assert plan.iterations.item() == D.TRAJ_STEPS
+    assert plan.iterations.item() == C.TRAJ_STEPS
     far = []
     for n in w0:
         d = st.view(n).detach().cpu().double() - w0[n]
@@ -178,10 +178,10 @@ def test_layerwise_plan_draws_the_same_masks(name):
     """The oracle uses one mask; both plans within its bound means both drew that mask."""
     tde, PG = _tde()
     B, Bplan = 5, 8
-    m, x, y = D.make_case(tde, name, B, Bplan)
+    m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
     st = m._store
-    orc = D.oracle(m, st, x, y, B, Bplan, 0)
-    o32 = D.oracle(m, st, x, y, B, Bplan, 0, dtype=torch.float32)
+    orc = O.oracle(m, st, x, y, B, Bplan, 0)
+    o32 = O.oracle(m, st, x, y, B, Bplan, 0, dtype=torch.float32)
     fused = _plan(PG, m, Bplan)
     lw = _plan(PG, m, Bplan, prefer="layerwise")
     assert lw.kind == "layerwise" and lw.compute_dtype == "fp32"
@@ -200,7 +200,7 @@ def test_rate_zero_is_the_model_without_the_layer():
     B, Bplan = 67, 67
     got = []
     for name in ("linear_rate0", "linear_plain"):
-        m, x, y = D.make_case(tde, name, B, Bplan)
+        m, x, y = C.make_case(tde, "dropout", name, B, Bplan)
         plan = _plan(PG, m, Bplan)
         assert not plan.drops and plan.step_word is None
         plan.train_step(x.cuda(), y.cuda(), B)

@@ -1,5 +1,6 @@
 """Every conv form and padded edge of the fused small-net plan (csrc/kernels/smallnet.hip,
-train/smallnet.py) against the float64 oracle of tests/smallnet_oracle.py, step mode "plain".
+train/smallnet.py) against the float64 oracle of tests/smallnet_oracle.py on the forms suite of
+tests/smallnet_cases.py, step mode "plain".
 
 Per (model, batch): every variable's gradient norm-wise relative to float64, bound = max(1e-5, 4 x the
 error of the fp32 torch CPU reference plan against the same oracle, computed on the spot); loss sum at
@@ -64,7 +65,7 @@ lenet5 / lenet5_nobias (use_bias=False on both convs: b_off < 0 in fwd_c, fwd_m,
                               pair's second tile is all clamp), results written over the input
   MaxPooling2D, Dense(120, relu), Dense(84, relu), Dense(10): float4 dense forward / backward, scalar head
 
-Masks 0 and 7 run in one fresh child process each (tests/_smallnet_forms_child.py): the library reads
+Masks 0 and 7 run in one fresh child process each (tests/_smallnet_child.py forms): the library reads
 TDE_SN_MFMA once per process.  Each child also runs one lenet5 step on unquantized randn data; its conv
 gradient hashes must differ from the in-process (mask 3) ones where the mask changes the summation order,
 otherwise the child tested the default forms.
@@ -82,67 +83,32 @@ A kernel with one output row dropped from the padded weight gradient and one tap
 gradient (both in bounds) fails the two `padded` cases at 0.35 - 0.39 on conv2d/kernel while
 tests/test_smallnet_gpu.py still passes.
 """
-import json
 import os
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import smallnet_cases as C
 import smallnet_oracle as O
+from smallnet_child import guard, run
 
 pytestmark = pytest.mark.gpu
-REPO = Path(__file__).resolve().parents[1]
-CHILD_TIMEOUT = 120     # s: a cold import of torch, loading the code objects, four small plans and their CPU
-#                         oracles (about 3 s warm)
-
-_CRASHED = []           # set when a child ends by signal or at its time limit: no GPU work after that
-_CHILDREN = {}
 
 
-def _guard():
-    if _CRASHED:
-        pytest.fail(f"not run: {_CRASHED[0]}")
-
-
-def _child(mask):
-    if mask in _CHILDREN:
-        return _CHILDREN[mask]
-    _guard()
-    env = dict(os.environ, PYTHONPATH=str(REPO), TDE_SN_MFMA=mask)
-    try:
-        p = subprocess.run([sys.executable, str(REPO / "tests" / "_smallnet_forms_child.py")], env=env,
-                           capture_output=True, text=True, timeout=CHILD_TIMEOUT, cwd=str(REPO))
-    except subprocess.TimeoutExpired as e:
-        _CRASHED.append(f"the TDE_SN_MFMA={mask} child hit its {CHILD_TIMEOUT} s limit")
-        pytest.fail(f"{_CRASHED[0]}\n{e.stdout}\n{e.stderr}")
-    if p.returncode < 0:
-        _CRASHED.append(f"the TDE_SN_MFMA={mask} child ended by signal {-p.returncode}")
-        pytest.fail(f"{_CRASHED[0]}\n{p.stdout}\n{p.stderr}")
-    assert p.returncode == 0, p.stdout + p.stderr
-    lines = [l for l in p.stdout.splitlines() if l.startswith("SMALLNET_FORMS ")]
-    assert len(lines) == 1, p.stdout + p.stderr
-    out = json.loads(lines[0][len("SMALLNET_FORMS "):])
-    assert out["mask"] == mask
-    _CHILDREN[mask] = out
-    return out
-
-
-@pytest.mark.parametrize("name,B,Bplan", O.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["forms"])
 def test_forms_default_mask(name, B, Bplan):
     """Every model and batch in-process (TDE_SN_MFMA default 3: MFMA forward and weight gradient, VALU
     input gradient for the compile-time geometries; the runtime-geometry kernels for everything else)."""
     import tensorflow_distributed_example_amd as tde
-    _guard()
-    O.check(O.measure(tde, name, B, Bplan))
+    guard()
+    O.check(O.measure(tde, "forms", name, B, Bplan))
 
 
 @pytest.mark.parametrize("mask", ["0", "7"])
 def test_forms_child_mask(mask):
     """lenet5, lenet5_nobias, geo3 (and the randn lenet5 step) with all VALU (0) / all MFMA (7) forms."""
-    out = _child(mask)
-    assert [(f["name"], f["data"]) for f in out["figs"]] == [(n, "grid") for n in O.FAST] + [("lenet5", "randn")]
+    out = run("forms", mask)
+    assert [(f["suite"], f["name"], f["data"]) for f in out["figs"]] == (
+        [("forms", n, "grid") for n in C.FAST["forms"]] + [("forms", "lenet5", "randn")])
     for fig in out["figs"]:
         O.check(fig)
 
@@ -153,13 +119,13 @@ def test_mask_took_effect():
     child ran the default forms.  Mask 7 changes only conv2's input gradient: conv1's kernel gradient
     (downstream of it) differs in bits, conv2's (same MFMA forms on the same operands) does not."""
     import tensorflow_distributed_example_amd as tde
-    _guard()
+    guard()
     assert os.environ.get("TDE_SN_MFMA", "3") == "3", "the in-process side of this test is the default mask"
-    B, Bplan = O.FAST_BATCH
-    h0 = [f for f in _child("0")["figs"] if f["data"] == "randn"][0]["conv_grad_hash"]
-    h7 = [f for f in _child("7")["figs"] if f["data"] == "randn"][0]["conv_grad_hash"]
-    _guard()
-    fig = O.measure(tde, "lenet5", B, Bplan, "randn")
+    B, Bplan = C.FAST_BATCH
+    h0 = [f for f in run("forms", "0")["figs"] if f["data"] == "randn"][0]["conv_grad_hash"]
+    h7 = [f for f in run("forms", "7")["figs"] if f["data"] == "randn"][0]["conv_grad_hash"]
+    guard()
+    fig = O.measure(tde, "forms", "lenet5", B, Bplan, "randn")
     O.check(fig)
     h3 = fig["conv_grad_hash"]
     c1, c2 = sorted(h3)          # conv2d/kernel, conv2d_1/kernel

@@ -1,5 +1,6 @@
 """The float64 small-net oracle (tests/smallnet_oracle.py) against the repository's own fp32
-``ReferencePlan`` on the CPU, for every model and batch of tests/test_smallnet_forms_gpu.py.
+``ReferencePlan`` on the CPU, for every model and batch of tests/test_smallnet_forms_gpu.py (the forms suite
+of tests/smallnet_cases.py), and on one model that needs every branch of the oracle's walker at once.
 
 Validates, without a GPU: the oracle's padding and pool conventions (asymmetric TF ``same`` pads, floor
 pooling), the quantizer's exactness claim (fp32 conv trunk == float64 bit for bit, and the sum of |terms|
@@ -47,6 +48,7 @@ the last digit with the CPU's conv / GEMM kernels).  Trunk exact everywhere; los
 import pytest
 import torch
 
+import smallnet_cases as C
 import smallnet_oracle as O
 
 
@@ -55,8 +57,8 @@ def test_models_are_smallnet_models():
     import tensorflow_distributed_example_amd as tde
     from tensorflow_distributed_example_amd.train import program as PG
     from tensorflow_distributed_example_amd.train import smallnet as SN
-    for name in O.MODELS:
-        m, _ = O.build(tde, name, 5)
+    for name in C.MODELS["forms"]:
+        m, _ = C.build(tde, "forms", name, 5)
         assert PG.match_convnet(m, m.loss) is None, name
         spec = SN.match_smallnet(m, m.loss)
         assert spec is not None, name
@@ -69,11 +71,11 @@ def test_grid_round():
     assert O.grid_round([0.3, -0.3, 0.031], 4).tolist() == [0.3125, -0.3125, 0.0]
 
 
-@pytest.mark.parametrize("name,B,Bplan", O.CASES)
+@pytest.mark.parametrize("name,B,Bplan", C.CASES["forms"])
 def test_oracle_matches_fp32_reference(name, B, Bplan):
     import tensorflow_distributed_example_amd as tde
-    m, x, y = O.make_case(tde, name, B, Bplan)
-    in_bits, w_bits = O.MODELS[name][2:]
+    m, x, y = C.make_case(tde, "forms", name, B, Bplan)
+    in_bits, w_bits = C.MODELS["forms"][name].bits
     exact, headroom = O.trunk_check(m, m._store, x, B, in_bits, w_bits)
     orc = O.oracle(m, m._store, x, y, B, Bplan)
     ref = O.reference_errors(tde, m, x, y, B, Bplan, orc)
@@ -103,11 +105,47 @@ def test_oracle_matches_fp32_reference(name, B, Bplan):
 def test_oracle_randn_case_matches_fp32_reference():
     """The unquantized LeNet-5 step of the mask-effect check."""
     import tensorflow_distributed_example_amd as tde
-    B, Bplan = O.FAST_BATCH
-    m, x, y = O.make_case(tde, "lenet5", B, Bplan, data="randn")
+    B, Bplan = C.FAST_BATCH
+    m, x, y = C.make_case(tde, "forms", "lenet5", B, Bplan, data="randn")
     orc = O.oracle(m, m._store, x, y, B, Bplan)
     ref = O.reference_errors(tde, m, x, y, B, Bplan, orc)
     for n, e in ref["grads"].items():
         print(f"[lenet5 randn] grad {n}: {e:.2g}")
         assert e < O.TOL, (n, e)
     assert ref["loss"] < O.TOL and ref["predict"] < O.TOL
+
+
+def test_oracle_walks_tanh_average_pool_and_dropout_in_one_model():
+    """``union``: a tanh conv, an average pool, a Dropout and a Dense ReLU, which ``match_smallnet`` accepts.
+    The oracle at step 0 in float64 against itself in fp32 with the same masks: every gradient and the loss
+    under TOL, the floor of ``bound`` (the dropout suite's CPU criterion, tests/test_smallnet_dropout.py), at a
+    seed where relu_near and margin hold.  Without masks it is the oracle of the same model built at rate 0."""
+    import tensorflow_distributed_example_amd as tde
+    from tensorflow_distributed_example_amd.train.smallnet import match_smallnet
+    B, Bplan = 5, 8
+    m, x, y = C.make_case(tde, "dropout", "union", B, Bplan)
+    spec = match_smallnet(m, m.loss)
+    assert spec is not None and [s["drop"] is not None for s in spec] == [False, True, False, False]
+    o64 = O.oracle(m, m._store, x, y, B, Bplan, 0)
+    o32 = O.oracle(m, m._store, x, y, B, Bplan, 0, dtype=torch.float32)
+    print(f"[union] relu_near={o64['relu_near']:.3g} margin={o64['margin']:.3g}")
+    assert o64["relu_near"] >= O.TIE and o64["margin"] >= O.TIE
+    assert set(o64["grads"]) == set(m._store.names(trainable=True))
+    for n, g in o64["grads"].items():
+        e = O.rel(o32["grads"][n], g)
+        print(f"[union] grad {n}: cpu-fp32 {e:.2g}")
+        assert torch.isfinite(g).all() and g.abs().max() > 0 and e < O.TOL, (n, e)
+    assert abs(o32["loss"] - o64["loss"]) / abs(o64["loss"]) < O.TOL
+    assert o32["correct"] == o64["correct"]
+    (dname, kept), = o64["dropped"].items()
+    assert 0 < (kept == 0).double().mean() < 1      # the mask was drawn, on the [B, 2, 2, 4] pool output
+    assert tuple(kept.shape) == (B, 2, 2, 4)
+    # step=None: no masks, the model built with rate 0
+    m0, x0, y0 = C.make_case(tde, "dropout", "union_rate0", B, Bplan)
+    assert torch.equal(x0, x) and torch.equal(y0, y)
+    free, zero = O.oracle(m, m._store, x, y, B, Bplan), O.oracle(m0, m0._store, x0, y0, B, Bplan, 0)
+    assert free["loss"] == zero["loss"] and torch.equal(free["out"], zero["out"])
+    assert len(free["grads"]) == len(zero["grads"]) == 6
+    for a, b in zip(free["grads"].values(), zero["grads"].values()):
+        assert torch.equal(a, b)
+    assert free["loss"] != o64["loss"]
