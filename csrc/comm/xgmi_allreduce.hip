@@ -663,7 +663,7 @@ static int xg_fill(XgArgs& a, float* grad, long long M, long long max_elems, voi
 }
 
 static int xg_set_apply(XgArgs& a, const TdeXgApply* o) {
-  if (!o || !o->w || (o->kind != kOptSGD && !o->m) || (o->kind == kOptAdam && (!o->v || !o->iterations))) return -7;
+  if (!o || !opt_kind_fused(o->kind) || !o->w || (o->kind != kOptSGD && !o->m) || (o->kind == kOptAdam && (!o->v || !o->iterations))) return -7;
   if ((((uintptr_t)o->w | (uintptr_t)o->m | (uintptr_t)o->v) & 15) || (o->sh && ((o->sh_lo & 3) || ((uintptr_t)o->sh & 7))))
     return -8;
   if (o->sht && (o->sh_cols <= 0 || !o->sh)) return -9;

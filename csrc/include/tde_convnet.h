@@ -718,7 +718,8 @@ namespace cnet {
 
 inline OptHyper hyper_of(const TdeStepOpt* o) { return OptHyper{o->kind, o->lr, o->mom, o->b1, o->b2, o->eps}; }
 inline bool opt_ok(const TdeStepOpt* o) {
-  return o->w && o->g && o->iterations && (o->kind == kOptSGD || o->m) && (o->kind != kOptAdam || o->v) &&
+  return opt_kind_fused(o->kind) && o->w && o->g && o->iterations && (o->kind == kOptSGD || o->m) &&
+         (o->kind != kOptAdam || o->v) &&
          (!o->hsnap || (o->hsrc_w2 && o->hsrc_b2 && o->hC >= 1 && o->hC <= 16 && !((uintptr_t)o->hsnap & 15)));
 }
 
@@ -760,7 +761,8 @@ inline int fill_bwd(BwdArgs& a, const float* x, const void* amax, int lda, const
                     long long* stamps, const TdeBwdOpt* opt) {
   if ((ldw1 & 7) || (ldPt & 7) || ldPt < B || lda < B || C < 1 || C > 16 || !hpre || !hzero || !labels) return -1;
   if ((((uintptr_t)hpre | (uintptr_t)hzero | (uintptr_t)b1) & 15)) return -2;
-  if (opt && (!opt->w || !opt->iterations || (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && !opt->v) ||
+  if (opt && (!opt_kind_fused(opt->kind) || (opt->commit.nr > 0 && !opt_kind_fused(opt->commit.h.kind)) || !opt->w || !opt->iterations ||
+              (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && !opt->v) ||
               ldw1 != HD || (opt->W1c && (opt->ldw1c & 3)) || (opt->off_w1 & 3) || opt->commit.nr > kFlatRanges ||
               (opt->commit.nr > 0 && !opt->commit.pend) || (b1 != nullptr) != (opt->off_b1 >= 0)))
     return -4;

@@ -7,12 +7,32 @@
 //   SGD        w -= lr*g
 //   momentum   v = mom*v - lr*g ; w += v          (nesterov: w += mom*v - lr*g)
 //   Adam       m,v moments ; w -= lr_t*m/(sqrt(v)+eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t)
+//   RMSprop    r = rho*r + (1-rho)*g*g ; w -= lr*g/(sqrt(r)+eps)                  (rho travels as b2)
+//   RMSprop with momentum
+//              r as above ; q = mom*q + lr*g/sqrt(r+eps) ; w -= q
+// Epsilon sits outside the square root without momentum and inside it with momentum: that is TF 2.x
+// Keras's own inconsistency (the dense kernels behind its RMSprop), kept so that both forms match it.
+// RMSprop's `rms` slot travels as `m` and its momentum accumulator as `v` (the slot order of
+// optimizers.RMSprop), so "uses m <=> kind != SGD" holds for every kind.
+//
+// opt_step / opt_lr_t / flat_apply know kinds 0..3 only and are inlined into the fused step kernels, the
+// deferred flush and the xGMI all-reduce; the RMSprop kinds exist in opt_step_x alone, which the
+// multi-tensor optimizer (optim.hip) and the small-net commit (smallnet.hip) call from a compile-time
+// variant.  Every other entry point refuses them (opt_kind_fused) instead of misreading them as Adam.
 #pragma once
 #include "tde_common.h"
 
 namespace tde {
 
-enum { kOptSGD = 0, kOptMomentum = 1, kOptNesterov = 2, kOptAdam = 3 };
+enum { kOptSGD = 0, kOptMomentum = 1, kOptNesterov = 2, kOptAdam = 3, kOptRMSprop = 4, kOptRMSpropMom = 5 };
+
+// The kinds opt_step knows: what the fused step kernels, the deferred flush and the xGMI all-reduce accept.
+__host__ __device__ __forceinline__ bool opt_kind_fused(int kind) { return kind >= kOptSGD && kind <= kOptAdam; }
+// Any known kind (opt_step_x).
+__host__ __device__ __forceinline__ bool opt_kind_known(int kind) { return kind >= kOptSGD && kind <= kOptRMSpropMom; }
+// Slot use: the first slot is passed as `m`, the second as `v`.
+__host__ __device__ __forceinline__ bool opt_uses_m(int kind) { return kind != kOptSGD; }
+__host__ __device__ __forceinline__ bool opt_uses_v(int kind) { return kind == kOptAdam || kind == kOptRMSpropMom; }
 
 struct OptHyper {
   int kind;
@@ -38,6 +58,16 @@ __device__ __forceinline__ float opt_step(const OptHyper& h, float lr_t, float w
   m = h.b1 * m + (1.f - h.b1) * g;
   v = h.b2 * v + (1.f - h.b2) * g * g;
   return w - lr_t * m / (sqrtf(v) + h.eps);
+}
+
+// Superset of opt_step: kinds 0..3 through opt_step, RMSprop (m = rms, v = the momentum accumulator) with
+// sqrtf and a true division in the order written at the top of this file.
+__device__ __forceinline__ float opt_step_x(const OptHyper& h, float lr_t, float w, float g, float& m, float& v) {
+  if (h.kind != kOptRMSprop && h.kind != kOptRMSpropMom) return opt_step(h, lr_t, w, g, m, v);
+  m = h.b2 * m + (1.f - h.b2) * g * g;
+  if (h.kind == kOptRMSprop) return w - h.lr * g / (sqrtf(m) + h.eps);
+  v = h.mom * v + h.lr * g / sqrtf(m + h.eps);
+  return w - v;
 }
 
 // Update of up to kFlatRanges element ranges of the flat parameter buffers

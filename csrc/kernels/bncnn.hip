@@ -2178,7 +2178,7 @@ TDE_API int tde_bncnn_reduce(int n, const int* cnt, const float* const* part, fl
   }
   a.stamps = next_stamps();
   if (opt) {
-    if (!opt->g || !opt->w || !opt->iterations || (opt->kind != kOptSGD && !opt->m) ||
+    if (!opt_kind_fused(opt->kind) || !opt->g || !opt->w || !opt->iterations || (opt->kind != kOptSGD && !opt->m) ||
         (opt->kind == kOptAdam && !opt->v))
       return -2;
     a.iterations = opt->iterations;

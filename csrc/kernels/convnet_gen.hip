@@ -811,7 +811,7 @@ TDE_API int tde_cgen_fwd(int CC, int HD, const float* x, const float* wc, const 
                          hipStream_t stream) {
   if (!tde_cgen_supported(CC, HD) || (W & 3) || W > 32 || H < 4 || W < 4 || ((H - 2) & 1) || ((W - 2) & 1))
     return -1;
-  if (fly && (!fly->pend || !fly->gwc || !fly->gbc || fly->grep < 1 || fly->grep > kMaxGrep || !fly->iter_prev ||
+  if (fly && (!opt_kind_fused(fly->kind) || !fly->pend || !fly->gwc || !fly->gbc || fly->grep < 1 || fly->grep > kMaxGrep || !fly->iter_prev ||
               (fly->kind != kOptSGD && (!fly->mwc || !fly->mbc)) || (fly->kind == kOptAdam && (!fly->vwc || !fly->vbc)) ||
               !fly->sw2 || !fly->sb2 || !fly->hsnap || fly->hC < 1 || fly->hC > 16))
     return -3;
@@ -839,13 +839,13 @@ TDE_API int tde_cgen_bwd(int CC, int HD, const float* x, const void* amax, int l
                          long long crep_stride, const TdeCgenHead* hopt, const FlatApply* fcommit,
                          const XgPush* push, int B, int H, int W, hipStream_t stream) {
   if (!tde_cgen_supported(CC, HD) || C < 1 || C > 16 || W > 32 || (W & 3)) return -1;
-  if (opt && (!opt->w || (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && (!opt->v || !opt->iterations))))
+  if (opt && (!opt_kind_fused(opt->kind) || !opt->w || (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && (!opt->v || !opt->iterations))))
     return -3;
   if (crep < 1 || crep > 64 || (crep > 1 && crep_stride < 10LL * CC)) return -4;
   if (push && push->nranks > 0 &&
       (opt || push->nranks > kXgMaxRanks || push->L <= 0 || (push->L & 3) || (push->off & 3) || !push->epoch))
     return -6;
-  if (hopt && (!opt || !fcommit || !fcommit->pend || fcommit->grep > kMaxGrep || fcommit->nr > kFlatRanges ||
+  if (hopt && (!opt || !fcommit || !opt_kind_fused(hopt->kind) || (fcommit->nr > 0 && !opt_kind_fused(fcommit->h.kind)) || !fcommit->pend || fcommit->grep > kMaxGrep || fcommit->nr > kFlatRanges ||
                !hopt->w || (hopt->kind != kOptSGD && !hopt->m) || (hopt->kind == kOptAdam && !hopt->v) ||
                !hopt->iterations || !hopt->pend_set || !hopt->iter_prev))
     return -5;

@@ -31,7 +31,7 @@ struct OptArgs {
   const OptSeg* segs;
   const int4* table;        // per block: {seg, kind(0=1d,1=tile), a, b}
   const long long* iterations;
-  int kind;                 // 0 sgd, 1 momentum, 2 nesterov, 3 adam
+  int kind;                 // 0 sgd, 1 momentum, 2 nesterov, 3 adam, 4 rmsprop, 5 rmsprop with momentum
   float lr, mom, b1, b2, eps, grad_scale;
   int zero_grad;
   const float* lr_ptr;      // optional device-resident lr (schedules)
@@ -44,40 +44,52 @@ struct Hyper {
   float lr, lr_t;
 };
 
+// EXT = false: kinds 0..3 (opt_step; the instruction stream these kinds always had).  EXT = true: the RMSprop
+// kinds (opt_step_x), launched for kinds 4 / 5 only: rms is `m`, the momentum accumulator `v` (kind 5 alone
+// reads or writes it).
+template <bool EXT>
+__device__ __forceinline__ bool uses_m(const OptArgs& a) { return EXT ? true : a.kind != 0; }
+template <bool EXT>
+__device__ __forceinline__ bool uses_v(const OptArgs& a) { return EXT ? a.kind == kOptRMSpropMom : a.kind == 3; }
+
+template <bool EXT>
 __device__ __forceinline__ float upd1(const OptArgs& a, float w, float g, float& m, float& v, const Hyper& h) {
   const OptHyper oh{a.kind, h.lr, a.mom, a.b1, a.b2, a.eps};
-  return opt_step(oh, h.lr_t, w, g * a.grad_scale, m, v);
+  return EXT ? opt_step_x(oh, h.lr_t, w, g * a.grad_scale, m, v) : opt_step(oh, h.lr_t, w, g * a.grad_scale, m, v);
 }
 
 // Update 4 consecutive elements at flat index i (16-byte aligned).
+template <bool EXT>
 __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& h) {
   float4 w = *reinterpret_cast<float4*>(a.w + i);
   const float4 g = *reinterpret_cast<float4*>(a.g + i);
   float4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
-  if (a.kind != 0) m = *reinterpret_cast<float4*>(a.m + i);
-  if (a.kind == 3) v = *reinterpret_cast<float4*>(a.v + i);
-  w.x = upd1(a, w.x, g.x, m.x, v.x, h);
-  w.y = upd1(a, w.y, g.y, m.y, v.y, h);
-  w.z = upd1(a, w.z, g.z, m.z, v.z, h);
-  w.w = upd1(a, w.w, g.w, m.w, v.w, h);
+  if (uses_m<EXT>(a)) m = *reinterpret_cast<float4*>(a.m + i);
+  if (uses_v<EXT>(a)) v = *reinterpret_cast<float4*>(a.v + i);
+  w.x = upd1<EXT>(a, w.x, g.x, m.x, v.x, h);
+  w.y = upd1<EXT>(a, w.y, g.y, m.y, v.y, h);
+  w.z = upd1<EXT>(a, w.z, g.z, m.z, v.z, h);
+  w.w = upd1<EXT>(a, w.w, g.w, m.w, v.w, h);
   *reinterpret_cast<float4*>(a.w + i) = w;
   if (a.zero_grad) *reinterpret_cast<float4*>(a.g + i) = float4{0.f, 0.f, 0.f, 0.f};
-  if (a.kind != 0) *reinterpret_cast<float4*>(a.m + i) = m;
-  if (a.kind == 3) *reinterpret_cast<float4*>(a.v + i) = v;
+  if (uses_m<EXT>(a)) *reinterpret_cast<float4*>(a.m + i) = m;
+  if (uses_v<EXT>(a)) *reinterpret_cast<float4*>(a.v + i) = v;
   return w;
 }
 
+template <bool EXT>
 __device__ __forceinline__ float upds(const OptArgs& a, size_t i, const Hyper& h) {
-  float m = a.kind != 0 ? a.m[i] : 0.f, v = a.kind == 3 ? a.v[i] : 0.f;
-  const float w = upd1(a, a.w[i], a.g[i], m, v, h);
+  float m = uses_m<EXT>(a) ? a.m[i] : 0.f, v = uses_v<EXT>(a) ? a.v[i] : 0.f;
+  const float w = upd1<EXT>(a, a.w[i], a.g[i], m, v, h);
   a.w[i] = w;
   if (a.zero_grad) a.g[i] = 0.f;
-  if (a.kind != 0) a.m[i] = m;
-  if (a.kind == 3) a.v[i] = v;
+  if (uses_m<EXT>(a)) a.m[i] = m;
+  if (uses_v<EXT>(a)) a.v[i] = v;
   return w;
 }
 
-__global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
+template <bool EXT>
+__device__ __forceinline__ void optim_apply(const OptArgs a) {
   __shared__ bf16 tile[kTileR][72];
   const int4 ent = a.table[blockIdx.x];
   const OptSeg s = a.segs[ent.x];
@@ -94,14 +106,14 @@ __global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
     for (int it = 0; it < kChunk / 1024; ++it) {
       const long long e = beg + it * 1024 + tid * 4;
       if (e + 4 <= end) {
-        const float4 w = upd4(a, (size_t)(s.off + e), h);
+        const float4 w = upd4<EXT>(a, (size_t)(s.off + e), h);
         if (s.sh_off >= 0) {
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
         }
       } else {
         for (long long q = e; q < end && q < e + 4; ++q) {
-          const float w = upds(a, (size_t)(s.off + q), h);
+          const float w = upds<EXT>(a, (size_t)(s.off + q), h);
           if (s.sh_off >= 0) a.shadow[s.sh_off + q] = f2bf(w);
         }
       }
@@ -117,13 +129,13 @@ __global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
       if (gr < s.rows) {
         const long long e = (long long)gr * s.cols + gc;
         if (vec && gc + 4 <= s.cols) {
-          const float4 w = upd4(a, (size_t)(s.off + e), h);
+          const float4 w = upd4<EXT>(a, (size_t)(s.off + e), h);
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           if (s.sh_off >= 0) *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
           *reinterpret_cast<bf16x4*>(&tile[r][c]) = hv;
         } else {
           for (int q = 0; q < 4 && gc + q < s.cols; ++q) {
-            const float w = upds(a, (size_t)(s.off + e + q), h);
+            const float w = upds<EXT>(a, (size_t)(s.off + e + q), h);
             const bf16 hv = f2bf(w);
             if (s.sh_off >= 0) a.shadow[s.sh_off + e + q] = hv;
             tile[r][c + q] = hv;
@@ -139,6 +151,14 @@ __global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
       if (gr < s.rows && gc < s.cols) a.shadow[s.sht_off + (long long)gc * s.rows + gr] = tile[r][c];
     }
   }
+}
+
+__global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
+  optim_apply<false>(a);
+}
+
+__global__ __launch_bounds__(256) void optim_apply_ext_kernel(OptArgs a) {
+  optim_apply<true>(a);
 }
 
 // Writes bf16 shadows from the current weights without updating (init/restore).
@@ -196,6 +216,7 @@ TDE_API int tde_flat_apply(float* w, float* g, float* m, float* v, const long lo
                            int kind, float lr, float mom, float b1, float b2, float eps, const int* ranges,
                            int nr, int grep, long long grep_stride, unsigned long long* count,
                            hipStream_t stream) {
+  if (!opt_kind_fused(kind)) return -1;   // flat_apply is opt_step: kinds 0..3
   if (nr < 0 || nr > kFlatRanges || (kind != kOptSGD && !m) || (kind == kOptAdam && (!v || !iterations)))
     return -1;
   FlatApply f{w, g, m, v, iterations, pend, OptHyper{kind, lr, mom, b1, b2, eps}, nr, {0}, {0}, grep, grep_stride, count};
@@ -247,11 +268,13 @@ TDE_API int tde_optim_apply(float* w, float* g, float* m, float* v, void* shadow
                             const long long* iterations, int kind, float lr, float mom, float b1,
                             float b2, float eps, float grad_scale, int zero_grad,
                             const float* lr_ptr, hipStream_t stream) {
+  if (!opt_kind_known(kind) || (opt_uses_m(kind) && !m) || (opt_uses_v(kind) && !v)) return -2;
   if (nblocks <= 0) return 0;
   if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return -1;
   OptArgs a{w, g, m, v, (bf16*)shadow, (const OptSeg*)segs_dev, (const int4*)table_dev,
             iterations, kind, lr, mom, b1, b2, eps, grad_scale, zero_grad, lr_ptr};
-  optim_apply_kernel<<<nblocks, 256, 0, stream>>>(a);
+  if (opt_kind_fused(kind)) optim_apply_kernel<<<nblocks, 256, 0, stream>>>(a);
+  else optim_apply_ext_kernel<<<nblocks, 256, 0, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;
 }

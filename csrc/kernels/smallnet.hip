@@ -1082,7 +1082,19 @@ struct SnWgradArgs {
   OptHyper h;
 };
 
+// EXT = false: gradient store, or the in-step update of kinds 0..3 (opt_step).  EXT = true: the in-step
+// update of the RMSprop kinds (opt_step_x; rms is `m`, the momentum accumulator `v`), launched for kinds
+// 4 / 5 with apply = 1 only, so the other kinds keep the program they had.
+template <bool EXT>
 __device__ __forceinline__ void sn_commit(const SnWgradArgs& a, int e, float grad, float lr_t) {
+  if (EXT) {
+    float m = a.m[e];
+    float v = a.h.kind == kOptRMSpropMom ? a.v[e] : 0.f;
+    a.w[e] = opt_step_x(a.h, lr_t, a.w[e], grad, m, v);
+    a.m[e] = m;
+    if (a.h.kind == kOptRMSpropMom) a.v[e] = v;
+    return;
+  }
   if (!a.apply) {
     a.g[e] = grad;
     return;
@@ -1094,8 +1106,8 @@ __device__ __forceinline__ void sn_commit(const SnWgradArgs& a, int e, float gra
   if (a.h.kind == kOptAdam) a.v[e] = v;
 }
 
-
-__global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
+template <bool EXT>
+__device__ __forceinline__ void sn_wgrad(const SnWgradArgs a) {
   __shared__ float red[8][33];
   const int blk = blockIdx.x, tid = threadIdx.x;
   const float lr_t = a.apply ? opt_lr_t(a.h, *a.iterations) : 0.f;
@@ -1137,7 +1149,7 @@ __global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
       for (int k = 0; k < 8; ++k) sum += red[k][pp];
       for (int r = 0; r < a.nr; ++r) {
         if (p >= a.r[r].part_lo && p < a.r[r].part_lo + a.r[r].n) {
-          sn_commit(a, a.r[r].flat_off + p - a.r[r].part_lo, sum, lr_t);
+          sn_commit<EXT>(a, a.r[r].flat_off + p - a.r[r].part_lo, sum, lr_t);
           break;
         }
       }
@@ -1183,10 +1195,18 @@ __global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
       const int i = i0 + 4 * fq + ii;
-      if (i < D.In) sn_commit(a, D.w_off + i * D.Co + j0 + fr, acc[ii], lr_t);
+      if (i < D.In) sn_commit<EXT>(a, D.w_off + i * D.Co + j0 + fr, acc[ii], lr_t);
     }
-    if (bias && fq == 0) sn_commit(a, D.b_off + j0 + fr, accb[0], lr_t);
+    if (bias && fq == 0) sn_commit<EXT>(a, D.b_off + j0 + fr, accb[0], lr_t);
   }
+}
+
+__global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
+  sn_wgrad<false>(a);
+}
+
+__global__ __launch_bounds__(256) void smallnet_wgrad_ext_kernel(SnWgradArgs a) {
+  sn_wgrad<true>(a);
 }
 
 }  // namespace tde
@@ -1277,7 +1297,8 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
 
 // ranges: nr x {part_lo, n, flat_off}; dense: nd x {In, Co, xo, go, w_off, b_off, blk0, nblk}.
 // Grid: block 0 metrics, then conv_nblk conv blocks, then the dense blocks.  apply = 0 stores the
-// gradients into g; apply = 1 applies the optimizer (kind, lr, mom, b1, b2, eps) to w / m / v.
+// gradients into g; apply = 1 applies the optimizer (kind 0..5, lr, mom, b1, b2, eps) to w / m / v
+// (RMSprop: m = rms, v = the momentum accumulator of kind 5; an unknown kind or a missing slot returns -2).
 // step (optional): device word that block 0 sets to *iterations, the step index of the next step's masks.
 TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
                                const float* part, int npart, const float* rec, int nrec, float* w, float* g, float* m,
@@ -1285,7 +1306,7 @@ TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int 
                                int kind, float lr, float mom, float b1, float b2, float eps, hipStream_t stream) {
   if (nr > 2 * kSnMaxLayers || nd > kSnMaxLayers || B <= 0) return -1;
   if (step && !iterations) return -2;
-  if (apply && (!iterations || (kind != kOptSGD && !m) || (kind == kOptAdam && !v))) return -2;
+  if (apply && (!opt_kind_known(kind) || !iterations || (opt_uses_m(kind) && !m) || (opt_uses_v(kind) && !v))) return -2;
   if (!apply && !g) return -2;
   SnWgradArgs a{};
   for (int r = 0; r < nr; ++r) a.r[r] = SnRange{ranges[3 * r], ranges[3 * r + 1], ranges[3 * r + 2]};
@@ -1314,7 +1335,8 @@ TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int 
   a.step = step;
   a.metrics = metrics;
   a.h = OptHyper{kind, lr, mom, b1, b2, eps};
-  smallnet_wgrad_kernel<<<nblk, 256, 0, stream>>>(a);
+  if (apply && !opt_kind_fused(kind)) smallnet_wgrad_ext_kernel<<<nblk, 256, 0, stream>>>(a);
+  else smallnet_wgrad_kernel<<<nblk, 256, 0, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;
 }

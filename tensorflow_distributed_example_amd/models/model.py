@@ -210,7 +210,7 @@ class Model:
     def compile(self, optimizer="rmsprop", loss=None, metrics=None, loss_weights=None, weighted_metrics=None,
                 run_eagerly=None, steps_per_execution=None, jit_compile=None, **kw):
         self._require_built()
-        self.optimizer = OP.get(optimizer if optimizer != "rmsprop" else "sgd")
+        self.optimizer = OP.get(optimizer)
         self.loss = LS.get(loss)
         self.compiled_metrics = list(metrics or [])
         self._metric_names = MT.resolve(metrics)

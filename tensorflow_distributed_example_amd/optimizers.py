@@ -1,6 +1,7 @@
 """Optimizers: Keras SGD (v2: distributed_with_keras.py:42,
 tf2_mnist_distributed.py:137), TF1 GradientDescentOptimizer
-(mnist_keras_distributed.py:111) and Adam (BASELINE north star).
+(mnist_keras_distributed.py:111), Adam (BASELINE north star) and RMSprop (the
+default of Keras's ``compile()``).
 
 On the GPU the update runs as ONE multi-tensor HIP kernel over the flat
 parameter buffer (csrc/kernels/optim.hip) that also zeroes gradients, refreshes
@@ -14,7 +15,10 @@ import math
 
 import torch
 
-KIND = {"sgd": 0, "momentum": 1, "nesterov": 2, "adam": 3}
+KIND = {"sgd": 0, "momentum": 1, "nesterov": 2, "adam": 3, "rmsprop": 4, "rmsprop_momentum": 5}
+# kinds the fused step kernels, the xGMI all-reduce and the parameter server apply themselves (opt_step in
+# csrc/include/tde_optim.h); the others run through the multi-tensor launch or the small-net commit only
+FUSED_KINDS = (0, 1, 2, 3)
 
 
 class Optimizer:
@@ -117,6 +121,50 @@ class Adam(Optimizer):
         return {**super().get_config(), "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
 
 
+class RMSprop(Optimizer):
+    """Keras ``RMSprop`` in the TF 2.x form.  Slots are TensorFlow's: ``rms`` and, with momentum,
+    ``momentum`` -- in that order, so ``rms`` travels as the kernels' first slot pointer.  Epsilon sits
+    outside the square root without momentum and inside it with momentum: TF's own inconsistency, kept."""
+
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, name="RMSprop",
+                 **kw):
+        super().__init__(kw.pop("lr", learning_rate), name)
+        self.rho, self.momentum, self.epsilon = float(rho), float(momentum), float(epsilon)
+        self.centered = bool(centered)
+        if self.centered:
+            raise ValueError("RMSprop(centered=True) needs a third slot (the mean gradient); the flat store "
+                             "and the kernel interfaces carry two slots")
+        if not 0.0 <= self.rho < 1.0:
+            raise ValueError("rho must be in [0, 1)")
+        if self.momentum < 0:
+            raise ValueError("momentum must be >= 0")
+
+    @property
+    def kind(self):
+        return "rmsprop_momentum" if self.momentum > 0 else "rmsprop"
+
+    def slot_names(self):
+        return ["rms", "momentum"] if self.momentum > 0 else ["rms"]
+
+    def hparams(self):
+        return dict(mom=self.momentum, b1=0.0, b2=self.rho, eps=self.epsilon)
+
+    @torch.no_grad()
+    def apply_reference(self, w, g, slots, step):
+        lr, r = self.learning_rate, slots["rms"]
+        r.mul_(self.rho).add_((1 - self.rho) * g * g)
+        if self.momentum > 0:
+            q = slots["momentum"]
+            q.mul_(self.momentum).add_(lr * g / (r + self.epsilon).sqrt())   # epsilon inside the root (TF)
+            w.sub_(q)
+        else:
+            w.sub_(lr * g / (r.sqrt() + self.epsilon))                        # epsilon outside the root (TF)
+
+    def get_config(self):
+        return {**super().get_config(), "rho": self.rho, "momentum": self.momentum, "epsilon": self.epsilon,
+                "centered": self.centered}
+
+
 def get(identifier):
     if isinstance(identifier, Optimizer):
         return identifier
@@ -126,4 +174,6 @@ def get(identifier):
             return SGD()
         if k == "adam":
             return Adam()
+        if k == "rmsprop":
+            return RMSprop()
     raise ValueError(f"unsupported optimizer {identifier!r}")

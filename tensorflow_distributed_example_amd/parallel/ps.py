@@ -202,6 +202,9 @@ class PSClient:
 
     def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7):
         """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms)."""
+        if int(kind) not in (0, 1, 2, 3):
+            raise ValueError(f"the parameter server applies optimizer kinds 0..3 only (got kind {kind}; RMSprop "
+                             "is not supported under ParameterServerStrategy)")
         for c in self.conns:
             c.lib.tde_ps_set_optimizer(c.h, int(kind), float(momentum), float(beta1), float(beta2), float(epsilon))
 

@@ -418,8 +418,8 @@ class BnCnnPlan(ReplicaPlan):
         if mode == "plain":
             return True
         if mode == "xgmi":   # data parallel: the xGMI all-reduce applies the update to the f32 weights
-            return self.optimizer is not None and self.device.type == "cuda"
-        return mode == "local" and self.optimizer is not None and self.device.type == "cuda" and \
+            return self._opt_fused() and self.device.type == "cuda"
+        return mode == "local" and self._opt_fused() and self.device.type == "cuda" and \
             self._bn_segs is not None
 
     def xg_apply_spec(self):

@@ -255,6 +255,13 @@ class Estimator:
             max_steps = int(math.ceil(max_steps))
         st = self._train_strategy()
         if isinstance(st, ParameterServerStrategy) and st.is_distributed:
+            from ..optimizers import FUSED_KINDS
+            opt = self.model.optimizer
+            if opt is not None and opt.kind_id not in FUSED_KINDS:
+                # the ps tasks apply the update themselves (TCP and device plane) and know SGD / momentum /
+                # Nesterov / Adam only: refuse before a connection is opened
+                raise ValueError(f"ParameterServerStrategy does not support the optimizer {opt.name} "
+                                 f"({opt.kind}): the parameter server applies SGD, momentum, Nesterov or Adam")
             return self._train_ps(st, input_fn, hooks, steps, max_steps, saving_listeners)
         return self._train_sync(st, input_fn, hooks, steps, max_steps, saving_listeners)
 

@@ -88,6 +88,12 @@ class ReplicaPlan:
     def supports_step_mode(self, mode):
         return mode == "plain"
 
+    def _opt_fused(self):
+        """The optimizer is one the fused step kernels and the xGMI all-reduce apply themselves (kinds 0..3,
+        ``opt_step``).  RMSprop is not: such a plan runs "plain", the multi-tensor launch applies it."""
+        from ..optimizers import FUSED_KINDS
+        return self.optimizer is not None and self.optimizer.kind_id in FUSED_KINDS
+
     def set_step_mode(self, mode):
         if not self.supports_step_mode(mode):
             raise ValueError(f"{self.kind} plan does not support step mode {mode!r}")
@@ -479,7 +485,7 @@ class ConvNetPlan(ReplicaPlan):
     def supports_step_mode(self, mode):
         if mode == "plain":
             return True
-        return self.optimizer is not None and self.device.type == "cuda" and mode in ("local", "xgmi")
+        return self._opt_fused() and self.device.type == "cuda" and mode in ("local", "xgmi")
 
     def _gconv(self, q):
         """Pointer that indexes parity q's conv gradients with the flat-buffer offsets."""
@@ -782,7 +788,7 @@ class ConvNetGenPlan(ReplicaPlan):
     def supports_step_mode(self, mode):
         if mode == "plain":
             return True
-        ok = self.optimizer is not None and self.device.type == "cuda"
+        ok = self._opt_fused() and self.device.type == "cuda"
         return ok and mode in ("xgmi", "local")
 
     def _gset(self, q, name):

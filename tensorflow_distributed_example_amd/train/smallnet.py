@@ -267,9 +267,11 @@ class SmallNetPlan(ReplicaPlan):
 
     # ------------------------------------------------------------------ step modes
     def supports_step_mode(self, mode):
-        # "xgmi": data parallel, the xGMI all-reduce applies the update to the f32 weights
-        return mode == "plain" or (mode in ("local", "xgmi") and self.optimizer is not None and
-                                   self.device.type == "cuda")
+        # "local": the weight-gradient launch applies the update, every optimizer kind (RMSprop included).
+        # "xgmi": data parallel, the xGMI all-reduce applies the update to the f32 weights (kinds 0..3).
+        if mode == "xgmi":
+            return self._opt_fused() and self.device.type == "cuda"
+        return mode == "plain" or (mode == "local" and self.optimizer is not None and self.device.type == "cuda")
 
     def xg_apply_spec(self):
         from .program import f32_xg_apply_spec
