@@ -230,7 +230,7 @@ __device__ __forceinline__ void shadow_store(const XgArgs& a, long long e, float
 
 // Optimizer step of the 4 elements e .. e+3 (e % 4 == 0) from their reduced sums gs: w, slots, shadows; grad zeroed.
 __device__ __forceinline__ void apply4(const XgArgs& a, float lr_t, long long e, float4 gs) {
-  const bool mom = a.h.kind != kOptSGD, adam = a.h.kind == kOptAdam;
+  const bool mom = opt_has_m(a.h.kind), adam = opt_has_v(a.h.kind);
   float4 w = *reinterpret_cast<const float4*>(a.w + e);
   float4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
   if (mom) m = *reinterpret_cast<const float4*>(a.m + e);
@@ -254,7 +254,7 @@ __device__ __forceinline__ void apply4(const XgArgs& a, float lr_t, long long e,
 }
 // The same for one element.
 __device__ __forceinline__ void apply1(const XgArgs& a, float lr_t, long long e, float g) {
-  const bool mom = a.h.kind != kOptSGD, adam = a.h.kind == kOptAdam;
+  const bool mom = opt_has_m(a.h.kind), adam = opt_has_v(a.h.kind);
   float m = mom ? a.m[e] : 0.f, v = adam ? a.v[e] : 0.f;
   const float w = opt_step(a.h, lr_t, a.w[e], g, m, v);
   a.w[e] = w;
@@ -297,7 +297,7 @@ __device__ __forceinline__ void gather_apply(const XgArgs& a, float lr_t, const 
 template <bool NT>
 __device__ __forceinline__ void apply_chunk(const XgArgs& a, float lr_t, long long g0, const float* red, long long n) {
   const int tid = threadIdx.x;
-  const bool mom = a.h.kind != kOptSGD, adam = a.h.kind == kOptAdam;
+  const bool mom = opt_has_m(a.h.kind), adam = opt_has_v(a.h.kind);
   long long nv = 0;
   if ((g0 & 3) == 0) {   // area offsets are multiples of 4 elements
     nv = n >> 2;
@@ -452,7 +452,7 @@ __global__ void __launch_bounds__(kXgWideThreads) xgmi_allreduce_kernel(XgLaunch
 
   // ---- phase 3: gather every reduced slice chunk back into the bucket (or apply the update)
   float lr_t = 0.f;
-  if (a.apply) lr_t = opt_lr_t(a.h, a.h.kind == kOptAdam ? *a.iterations : 0);
+  if (a.apply) lr_t = opt_lr_t(a.h, opt_uses_t(a.h.kind) ? *a.iterations : 0);
   miss2 = await(a.peer[r], parity, 1, N, blk, epoch, a.timeout_ticks, a.err, 2u, seen2, !UNCACHED || a.acquire);
   XG_STAMP(5);
   const float* out = area(a.peer[r], 1, parity, cap);
@@ -600,8 +600,7 @@ TDE_API long long tde_xgmi_epoch(void* epoch) {
 // Fused form: SUM all-reduce of `grad` and the optimizer step of every element on every rank
 // (w/m/v flat like grad; shadows as in XgArgs); grad is left zeroed.
 struct TdeXgApply {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float *w, *m, *v;
   const long long* iterations;
   void* sh; long long sh_lo, sh_hi;
@@ -663,7 +662,7 @@ static int xg_fill(XgArgs& a, float* grad, long long M, long long max_elems, voi
 }
 
 static int xg_set_apply(XgArgs& a, const TdeXgApply* o) {
-  if (!o || !opt_kind_fused(o->kind) || !o->w || (o->kind != kOptSGD && !o->m) || (o->kind == kOptAdam && (!o->v || !o->iterations))) return -7;
+  if (!o || !opt_kind_fused(o->h.kind) || !o->w || !opt_slots_ok(o->h.kind, o->m, o->v) || (opt_uses_t(o->h.kind) && !o->iterations)) return -7;
   if ((((uintptr_t)o->w | (uintptr_t)o->m | (uintptr_t)o->v) & 15) || (o->sh && ((o->sh_lo & 3) || ((uintptr_t)o->sh & 7))))
     return -8;
   if (o->sht && (o->sh_cols <= 0 || !o->sh)) return -9;
@@ -678,7 +677,7 @@ static int xg_set_apply(XgArgs& a, const TdeXgApply* o) {
   a.sh_cols = o->sh_cols;
   a.sht_ld = o->sht_ld;
   a.iterations = o->iterations;
-  a.h = OptHyper{o->kind, o->lr, o->mom, o->b1, o->b2, o->eps};
+  a.h = o->h;
   a.push_lo = o->push_lo;
   a.push_hi = o->push_hi;
   if (o->nrep > 1 && (!o->rep || o->nrep > kMaxGrep || o->rep_lo < 0 || o->rep_hi < o->rep_lo ||

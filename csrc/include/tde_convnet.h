@@ -147,8 +147,8 @@ struct ConvOperand {
 #pragma unroll
       for (int r = 0; r < kMaxGrep; ++r) g[r] = gp[min(r, a.grep - 1) * a.grep_stride];
       // a slot the optimizer does not have reads the weight again and counts as 0
-      m = *(a.h.kind != kOptSGD ? (isb ? a.mbc + j : a.mwc + j) : wp);
-      v = *(a.h.kind == kOptAdam ? (isb ? a.vbc + j : a.vwc + j) : wp);
+      m = *(opt_has_m(a.h.kind) ? (isb ? a.mbc + j : a.mwc + j) : wp);
+      v = *(opt_has_v(a.h.kind) ? (isb ? a.vbc + j : a.vwc + j) : wp);
     }
   }
   // the weight in effect: the optimizer step of w while the update is pending (replicas summed in order)
@@ -157,8 +157,8 @@ struct ConvOperand {
     float gs = g[0];
 #pragma unroll
     for (int r = 1; r < kMaxGrep; ++r) gs += r < a.grep ? g[r] : 0.f;
-    const long long t = a.h.kind == kOptAdam ? iterations : 0;
-    float ms = a.h.kind != kOptSGD ? m : 0.f, vs = a.h.kind == kOptAdam ? v : 0.f;
+    const long long t = opt_uses_t(a.h.kind) ? iterations : 0;
+    float ms = opt_has_m(a.h.kind) ? m : 0.f, vs = opt_has_v(a.h.kind) ? v : 0.f;
     return pend ? opt_step(a.h, opt_lr_t(a.h, t), w, gs, ms, vs) : w;
   }
 };
@@ -186,9 +186,9 @@ __device__ __forceinline__ void fwd_stage_conv(const FwdArgs& a, float* wcs, int
 #pragma unroll
       for (int r = 1; r < kMaxGrep; ++r) g += gv[r];
       float m = 0.f, v = 0.f;
-      if (a.h.kind != kOptSGD) m = isb ? a.mbc[j] : a.mwc[j];
-      if (a.h.kind == kOptAdam) v = isb ? a.vbc[j] : a.vwc[j];
-      const long long t = a.h.kind == kOptAdam ? *a.iterations : 0;
+      if (opt_has_m(a.h.kind)) m = isb ? a.mbc[j] : a.mwc[j];
+      if (opt_has_v(a.h.kind)) v = isb ? a.vbc[j] : a.vwc[j];
+      const long long t = opt_uses_t(a.h.kind) ? *a.iterations : 0;
       if (*a.pend) w = opt_step(a.h, opt_lr_t(a.h, t), w, g, m, v);
     }
     wcs[i] = w;
@@ -309,8 +309,8 @@ struct FlatPrefetch {
       if (e[k] >= 0) {
         w[k] = f.w[e[k]];
         g[k] = flat_grad(f, e[k]);
-        if (f.h.kind != kOptSGD) m[k] = f.m[e[k]];
-        if (f.h.kind == kOptAdam) v[k] = f.v[e[k]];
+        if (opt_has_m(f.h.kind)) m[k] = f.m[e[k]];
+        if (opt_has_v(f.h.kind)) v[k] = f.v[e[k]];
       }
     }
   }
@@ -321,8 +321,8 @@ struct FlatPrefetch {
       if (e[k] < 0) continue;
       f.w[e[k]] = opt_step(f.h, lr_t, w[k], g[k], m[k], v[k]);
       flat_grad_zero(f, e[k]);
-      if (f.h.kind != kOptSGD) f.m[e[k]] = m[k];
-      if (f.h.kind == kOptAdam) f.v[e[k]] = v[k];
+      if (opt_has_m(f.h.kind)) f.m[e[k]] = m[k];
+      if (opt_has_v(f.h.kind)) f.v[e[k]] = v[k];
     }
   }
 };
@@ -554,8 +554,8 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
       const long long e = head_var(a, tl, i);
       if (e < 0) continue;
       hwv[i] = a.hw[e];
-      if (MODE == 2 && a.h.kind != kOptSGD) hmv[i] = a.hm[e];
-      if (MODE == 2 && a.h.kind == kOptAdam) hvv[i] = a.hv[e];
+      if (MODE == 2 && opt_has_m(a.h.kind)) hmv[i] = a.hm[e];
+      if (MODE == 2 && opt_has_v(a.h.kind)) hvv[i] = a.hv[e];
     }
     if (a.commit.nr > 0) {
       cpend = *a.commit.pend;
@@ -636,8 +636,8 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
     if (e < 0) continue;
     float m = hmv[i], v = hvv[i];
     a.hw[e] = opt_step(a.h, lr_t, hwv[i], gv[i], m, v);
-    if (MODE == 2 && a.h.kind != kOptSGD) a.hm[e] = m;
-    if (MODE == 2 && a.h.kind == kOptAdam) a.hv[e] = v;
+    if (MODE == 2 && opt_has_m(a.h.kind)) a.hm[e] = m;
+    if (MODE == 2 && opt_has_v(a.h.kind)) a.hv[e] = v;
   }
   // the previous step's conv update (its forward used it on the fly; this launch does not read the
   // conv weights): commit it, clear its flag; flag this step's update (the trunk's atomics)
@@ -687,8 +687,7 @@ __device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 a
 // Fused-step optimizer description shared by the convnet forward entry points (ctypes struct):
 // slots m/v flat like w; iterations = the device step counter.
 struct TdeStepOpt {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float *w, *g, *m, *v;
   const long long* iterations;
   int* pend;
@@ -701,8 +700,7 @@ struct TdeStepOpt {
 
 // Fused-step description of the backward (ctypes struct).
 struct TdeBwdOpt {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float *w, *m, *v;                   // flat buffers
   long long off_w1, off_w2, off_b2, off_b1;
   void* W1c; int ldw1c;               // bf16: transposed shadow (nullable)
@@ -716,10 +714,8 @@ struct TdeBwdOpt {
 namespace tde {
 namespace cnet {
 
-inline OptHyper hyper_of(const TdeStepOpt* o) { return OptHyper{o->kind, o->lr, o->mom, o->b1, o->b2, o->eps}; }
 inline bool opt_ok(const TdeStepOpt* o) {
-  return opt_kind_fused(o->kind) && o->w && o->g && o->iterations && (o->kind == kOptSGD || o->m) &&
-         (o->kind != kOptAdam || o->v) &&
+  return opt_kind_fused(o->h.kind) && o->w && o->g && o->iterations && opt_slots_ok(o->h.kind, o->m, o->v) &&
          (!o->hsnap || (o->hsrc_w2 && o->hsrc_b2 && o->hC >= 1 && o->hC <= 16 && !((uintptr_t)o->hsnap & 15)));
 }
 
@@ -738,7 +734,7 @@ inline void fill_fwd_opt(FwdArgs& a, const TdeStepOpt* opt, long long off_wc, lo
     a.vwc = opt->v ? opt->v + off_wc : nullptr;
     a.vbc = opt->v ? opt->v + off_bc : nullptr;
     a.iterations = opt->iterations;
-    a.h = hyper_of(opt);
+    a.h = opt->h;
     a.grep = opt->grep > 1 ? opt->grep : 1;
     a.grep_stride = opt->grep_stride;
     a.fly_count = opt->fly_count;
@@ -761,8 +757,8 @@ inline int fill_bwd(BwdArgs& a, const float* x, const void* amax, int lda, const
                     long long* stamps, const TdeBwdOpt* opt) {
   if ((ldw1 & 7) || (ldPt & 7) || ldPt < B || lda < B || C < 1 || C > 16 || !hpre || !hzero || !labels) return -1;
   if ((((uintptr_t)hpre | (uintptr_t)hzero | (uintptr_t)b1) & 15)) return -2;
-  if (opt && (!opt_kind_fused(opt->kind) || (opt->commit.nr > 0 && !opt_kind_fused(opt->commit.h.kind)) || !opt->w || !opt->iterations ||
-              (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && !opt->v) ||
+  if (opt && (!opt_kind_fused(opt->h.kind) || (opt->commit.nr > 0 && !opt_kind_fused(opt->commit.h.kind)) || !opt->w || !opt->iterations ||
+              !opt_slots_ok(opt->h.kind, opt->m, opt->v) ||
               ldw1 != HD || (opt->W1c && (opt->ldw1c & 3)) || (opt->off_w1 & 3) || opt->commit.nr > kFlatRanges ||
               (opt->commit.nr > 0 && !opt->commit.pend) || (b1 != nullptr) != (opt->off_b1 >= 0)))
     return -4;
@@ -818,7 +814,7 @@ inline int fill_bwd(BwdArgs& a, const float* x, const void* amax, int lda, const
     a.off_b1 = opt->off_b1;
     a.iterations = opt->iterations;
     a.iter_prev = opt->iter_prev;
-    a.h = OptHyper{opt->kind, opt->lr, opt->mom, opt->b1, opt->b2, opt->eps};
+    a.h = opt->h;
     a.commit = opt->commit;
     a.pend_set = opt->pend_set;
     a.crep = opt->crep > 1 ? opt->crep : 1;

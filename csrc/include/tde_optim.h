@@ -15,10 +15,15 @@
 // RMSprop's `rms` slot travels as `m` and its momentum accumulator as `v` (the slot order of
 // optimizers.RMSprop), so "uses m <=> kind != SGD" holds for every kind.
 //
-// opt_step / opt_lr_t / flat_apply know kinds 0..3 only and are inlined into the fused step kernels, the
-// deferred flush and the xGMI all-reduce; the RMSprop kinds exist in opt_step_x alone, which the
+// opt_step<false> / opt_lr_t / flat_apply know kinds 0..3 only and are inlined into the fused step kernels, the
+// deferred flush and the xGMI all-reduce; the RMSprop kinds exist in opt_step<true> alone, which the
 // multi-tensor optimizer (optim.hip) and the small-net commit (smallnet.hip) call from a compile-time
 // variant.  Every other entry point refuses them (opt_kind_fused) instead of misreading them as Adam.
+//
+// Which kind is which and which slots a kind has is decided here: kernels ask opt_has_m / opt_has_v /
+// opt_uses_t, entry points opt_kind_* / opt_slots_ok.  Two sites do not go through the helpers, each with a
+// comment that says why: the bf16 backward in convnet.hip spells the two slot compares out, and flat_apply
+// below keeps its own load / step / store.
 #pragma once
 #include "tde_common.h"
 
@@ -26,14 +31,25 @@ namespace tde {
 
 enum { kOptSGD = 0, kOptMomentum = 1, kOptNesterov = 2, kOptAdam = 3, kOptRMSprop = 4, kOptRMSpropMom = 5 };
 
-// The kinds opt_step knows: what the fused step kernels, the deferred flush and the xGMI all-reduce accept.
+// The kinds opt_step<false> knows: what the fused step kernels, the deferred flush and the xGMI all-reduce accept.
 __host__ __device__ __forceinline__ bool opt_kind_fused(int kind) { return kind >= kOptSGD && kind <= kOptAdam; }
-// Any known kind (opt_step_x).
+// Any known kind (opt_step<true>).
 __host__ __device__ __forceinline__ bool opt_kind_known(int kind) { return kind >= kOptSGD && kind <= kOptRMSpropMom; }
-// Slot use: the first slot is passed as `m`, the second as `v`.
+// Slot use, any known kind: the first slot is passed as `m`, the second as `v`.
 __host__ __device__ __forceinline__ bool opt_uses_m(int kind) { return kind != kOptSGD; }
 __host__ __device__ __forceinline__ bool opt_uses_v(int kind) { return kind == kOptAdam || kind == kOptRMSpropMom; }
+// Entry points: the slot buffers the kind reads and writes are there.
+inline bool opt_slots_ok(int kind, const void* m, const void* v) { return (!opt_uses_m(kind) || m) && (!opt_uses_v(kind) || v); }
+// Only Adam's step size depends on the step counter (opt_lr_t).
+__host__ __device__ __forceinline__ bool opt_uses_t(int kind) { return kind == kOptAdam; }
+// Slot use inside a kernel, one compare each.  EXT = false: a kernel whose entry point admits kinds 0..3 only.
+// EXT = true: a variant launched for the RMSprop kinds only.
+template <bool EXT = false>
+__device__ __forceinline__ bool opt_has_m(int kind) { return EXT ? true : kind != kOptSGD; }
+template <bool EXT = false>
+__device__ __forceinline__ bool opt_has_v(int kind) { return EXT ? kind == kOptRMSpropMom : kind == kOptAdam; }
 
+// Head of every optimizer argument struct of the C ABI (ctypes: ops/kernels.py OptHyper).
 struct OptHyper {
   int kind;
   float lr, mom, b1, b2, eps;
@@ -47,8 +63,18 @@ __device__ __forceinline__ float opt_lr_t(const OptHyper& h, long long t) {
   return h.lr * sqrtf(1.f - __powf(h.b2, tf)) / (1.f - __powf(h.b1, tf));
 }
 
-// One element: returns the new weight, updates the slots in place.
+// One element: returns the new weight, updates the slots in place.  EXT = false: kinds 0..3.  EXT = true: also
+// RMSprop (m = rms, v = the momentum accumulator) with sqrtf and a true division in the order written at the
+// top of this file.
+template <bool EXT = false>
 __device__ __forceinline__ float opt_step(const OptHyper& h, float lr_t, float w, float g, float& m, float& v) {
+  if constexpr (EXT) {
+    if (h.kind != kOptRMSprop && h.kind != kOptRMSpropMom) return opt_step<false>(h, lr_t, w, g, m, v);
+    m = h.b2 * m + (1.f - h.b2) * g * g;
+    if (h.kind == kOptRMSprop) return w - h.lr * g / (sqrtf(m) + h.eps);
+    v = h.mom * v + h.lr * g / sqrtf(m + h.eps);
+    return w - v;
+  }
   if (h.kind == kOptSGD) return w - h.lr * g;
   if (h.kind == kOptMomentum || h.kind == kOptNesterov) {
     const float nv = h.mom * m - h.lr * g;
@@ -60,14 +86,23 @@ __device__ __forceinline__ float opt_step(const OptHyper& h, float lr_t, float w
   return w - lr_t * m / (sqrtf(v) + h.eps);
 }
 
-// Superset of opt_step: kinds 0..3 through opt_step, RMSprop (m = rms, v = the momentum accumulator) with
-// sqrtf and a true division in the order written at the top of this file.
-__device__ __forceinline__ float opt_step_x(const OptHyper& h, float lr_t, float w, float g, float& m, float& v) {
-  if (h.kind != kOptRMSprop && h.kind != kOptRMSpropMom) return opt_step(h, lr_t, w, g, m, v);
-  m = h.b2 * m + (1.f - h.b2) * g * g;
-  if (h.kind == kOptRMSprop) return w - h.lr * g / (sqrtf(m) + h.eps);
-  v = h.mom * v + h.lr * g / sqrtf(m + h.eps);
-  return w - v;
+// The step at element e of flat buffers: loads the slots the kind has, steps from weight w0, stores the
+// weight and those slots, returns the new weight.  (I: the caller's index type, so its address math stays.)
+template <bool EXT = false, class I>
+__device__ __forceinline__ float opt_step_at(const OptHyper& h, float lr_t, float w0, float* w, float* m, float* v, I e,
+                                             float g) {
+  float ms = opt_has_m<EXT>(h.kind) ? m[e] : 0.f;
+  float vs = opt_has_v<EXT>(h.kind) ? v[e] : 0.f;
+  const float wn = opt_step<EXT>(h, lr_t, w0, g, ms, vs);
+  w[e] = wn;
+  if (opt_has_m<EXT>(h.kind)) m[e] = ms;
+  if (opt_has_v<EXT>(h.kind)) v[e] = vs;
+  return wn;
+}
+// ... from the stored weight.
+template <bool EXT = false, class I>
+__device__ __forceinline__ float opt_step_at(const OptHyper& h, float lr_t, float* w, float* m, float* v, I e, float g) {
+  return opt_step_at<EXT>(h, lr_t, w[e], w, m, v, e, g);
 }
 
 // Update of up to kFlatRanges element ranges of the flat parameter buffers
@@ -109,12 +144,14 @@ __device__ __forceinline__ void flat_apply(const FlatApply& f, long long t, int 
   for (int r = 0; r < f.nr; ++r) {
     for (int i = tid; i < f.n[r]; i += nt) {
       const int e = f.lo[r] + i;
-      float m = f.h.kind != kOptSGD ? f.m[e] : 0.f;
-      float v = f.h.kind == kOptAdam ? f.v[e] : 0.f;
+      // written out, not opt_step_at: with the gradient zeroed after the slot stores the kernels that inline
+      // this grew registers and SGPR spills (profiles/opt_descriptor/NOTES.md)
+      float m = opt_has_m(f.h.kind) ? f.m[e] : 0.f;
+      float v = opt_has_v(f.h.kind) ? f.v[e] : 0.f;
       f.w[e] = opt_step(f.h, lr_t, f.w[e], flat_grad(f, e), m, v);
       flat_grad_zero(f, e);
-      if (f.h.kind != kOptSGD) f.m[e] = m;
-      if (f.h.kind == kOptAdam) f.v[e] = v;
+      if (opt_has_m(f.h.kind)) f.m[e] = m;
+      if (opt_has_v(f.h.kind)) f.v[e] = v;
     }
   }
 }

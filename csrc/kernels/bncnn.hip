@@ -1688,10 +1688,7 @@ __device__ __forceinline__ void reduce_commit(const ReduceArgs& a, int j, long l
     return;
   }
   const long long f = (a.out[j] - a.g) + e;
-  float m = a.h.kind != kOptSGD ? a.m[f] : 0.f, vv = a.h.kind == kOptAdam ? a.v[f] : 0.f;
-  a.w[f] = opt_step(a.h, opt_lr_t(a.h, t), a.w[f], gs, m, vv);
-  if (a.h.kind != kOptSGD) a.m[f] = m;
-  if (a.h.kind == kOptAdam) a.v[f] = vv;
+  opt_step_at(a.h, opt_lr_t(a.h, t), a.w, a.m, a.v, f, gs);
   if (inplace) a.out[j][e] = 0.f;
 }
 
@@ -1708,7 +1705,7 @@ __global__ __launch_bounds__(NTH) void reduce_kernel(ReduceArgs a) {
     if (e0 >= len) return;
     const int cnt = a.cnt[j];
     const float* p = a.part[j];
-    const long long t = a.apply && a.h.kind == kOptAdam ? *a.iterations : 0;
+    const long long t = a.apply && opt_uses_t(a.h.kind) ? *a.iterations : 0;
     float4 v[kWideCnt];
 #pragma unroll
     for (int u = 0; u < kWideCnt; ++u)
@@ -1737,7 +1734,7 @@ __global__ __launch_bounds__(NTH) void reduce_kernel(ReduceArgs a) {
   const int cnt = a.cnt[j];
   const float* p = a.part[j];
   const long long ec = e < len ? e : len - 1;
-  const long long t = a.apply && a.h.kind == kOptAdam ? *a.iterations : 0;
+  const long long t = a.apply && opt_uses_t(a.h.kind) ? *a.iterations : 0;
   float s = 0.f;
   for (int b0 = q; b0 < cnt; b0 += 128) {
     float v[32];
@@ -2160,8 +2157,7 @@ TDE_API int tde_bncnn_conv_bwd(const TdeBnGeo* gg, int B, const float* z, const 
 // n segments: part[j] holds cnt[j] partials of len[j] floats, summed in order into out[j] (views of the
 // flat bucket g).  opt (nullable): apply the optimizer step instead of storing (see reduce_kernel).
 struct TdeBnOpt {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float *g, *w, *m, *v;
   const long long* iterations;
 };
@@ -2178,8 +2174,7 @@ TDE_API int tde_bncnn_reduce(int n, const int* cnt, const float* const* part, fl
   }
   a.stamps = next_stamps();
   if (opt) {
-    if (!opt_kind_fused(opt->kind) || !opt->g || !opt->w || !opt->iterations || (opt->kind != kOptSGD && !opt->m) ||
-        (opt->kind == kOptAdam && !opt->v))
+    if (!opt_kind_fused(opt->h.kind) || !opt->g || !opt->w || !opt->iterations || !opt_slots_ok(opt->h.kind, opt->m, opt->v))
       return -2;
     a.iterations = opt->iterations;
     a.apply = 1;
@@ -2187,7 +2182,7 @@ TDE_API int tde_bncnn_reduce(int n, const int* cnt, const float* const* part, fl
     a.w = opt->w;
     a.m = opt->m;
     a.v = opt->v;
-    a.h = OptHyper{opt->kind, opt->lr, opt->mom, opt->b1, opt->b2, opt->eps};
+    a.h = opt->h;
   }
   int blocks = 0;
   for (int j = 0; j < n; ++j) {
@@ -2205,4 +2200,10 @@ TDE_API int tde_bncnn_reduce(int n, const int* cnt, const float* const* part, fl
   reduce_kernel<<<blocks, NTH, 0, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;
+}
+
+// Size of the ctypes-mirrored struct (tests/test_abi.py): out = {TdeBnOpt}.
+TDE_API int tde_bncnn_abi_sizes(long long* out, int n) {
+  if (n > 0) out[0] = (long long)sizeof(TdeBnOpt);
+  return 1;
 }

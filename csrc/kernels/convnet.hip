@@ -232,6 +232,8 @@ __global__ __launch_bounds__(1024) void convnet_bwd_kernel(BwdArgs a) {
         const size_t e = (size_t)(p0 * CC + row) * HD + nt * 16 + fr;
         wp[i][r] = row < nrow ? a.w1[e] : 0.f;
         if (MODE == 2) {
+          // the slot rule (opt_has_m / opt_has_v, tde_optim.h) spelled out, here and at the stores below: through
+          // the helpers this kernel's register allocation changed (123 -> 222 spilled VGPRs)
           mp[i % NS][r] = (row < nrow && a.h.kind != kOptSGD) ? a.m1[e] : 0.f;
           vp[i % NS][r] = (row < nrow && a.h.kind == kOptAdam) ? a.v1[e] : 0.f;
         }
@@ -488,7 +490,7 @@ TDE_API int tde_convnet_bwd(const float* x, const void* amax, int lda, const flo
   }
   const dim3 grid((P + PPW - 1) / PPW + 1);   // + the head workgroup
   if (!opt) convnet_bwd_kernel<0><<<grid, 1024, kBwdLds, stream>>>(a);
-  else if (opt->kind == kOptSGD) convnet_bwd_kernel<1><<<grid, 1024, kBwdLds, stream>>>(a);
+  else if (opt->h.kind == kOptSGD) convnet_bwd_kernel<1><<<grid, 1024, kBwdLds, stream>>>(a);
   else convnet_bwd_kernel<2><<<grid, 1024, kBwdLds, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;

@@ -325,8 +325,8 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const size_t e = (size_t)(p * CC + rt * 16 + fq * 4 + r) * HD + nt * 16 + fr;
-      if (a.h.kind != kOptSGD) mp[r] = a.m1[e];
-      if (a.h.kind == kOptAdam) vp[r] = a.v1[e];
+      if (opt_has_m(a.h.kind)) mp[r] = a.m1[e];
+      if (opt_has_v(a.h.kind)) vp[r] = a.v1[e];
     }
   }
 
@@ -442,8 +442,8 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
         const size_t e = (size_t)(p * CC + row) * HD + col;
         float m = mp[r], v = vp[r];
         a.w1[e] = opt_step(a.h, lr_t, W1s[row * GS32 + col], accw[r], m, v);
-        if (MODE == 2 && a.h.kind != kOptSGD) a.m1[e] = m;
-        if (MODE == 2 && a.h.kind == kOptAdam) a.v1[e] = v;
+        if (MODE == 2 && opt_has_m(a.h.kind)) a.m1[e] = m;
+        if (MODE == 2 && opt_has_v(a.h.kind)) a.v1[e] = v;
       }
     } else if (a.push.nranks > 0) {
       // fused DP exchange: this position's complete dW1 rows [32][64] are staged in W1s (free after the
@@ -529,7 +529,7 @@ TDE_API int tde_convnet_bwd_f32(const float* x, const void* amax, int lda, const
   }
   const dim3 grid(P + 1);   // one workgroup per pooled position + the head workgroup
   if (!opt) convnet32_bwd_kernel<0><<<grid, 1024, kBwd32Lds, stream>>>(a);
-  else if (opt->kind == kOptSGD) convnet32_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
+  else if (opt->h.kind == kOptSGD) convnet32_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
   else convnet32_bwd_kernel<2><<<grid, 1024, kBwd32Lds, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;

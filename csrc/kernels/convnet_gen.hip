@@ -47,8 +47,7 @@ __host__ __device__ constexpr int xr_stride(int W) { return XRW * W + ((2 - (XRW
 // while *pend (its gradient: grep replicas gwc / gbc + r * grep_stride; the slots at the conv elements;
 // Adam's t = *iter_prev), and the head variables copied into the snapshot the backward's trunk reads.
 struct TdeCgenFly {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   const int* pend;
   const float* gwc; const float* gbc; int grep; long long grep_stride;
   const float* mwc; const float* mbc; const float* vwc; const float* vbc;
@@ -122,8 +121,8 @@ __global__ __launch_bounds__(256) void cgen_fwd_kernel(GFwdArgs a) {
     // the conv weights in effect: with the previous step's update (pending) applied on the fly
     const TdeCgenFly& f = a.fly;
     const bool fly = a.fly_on && *f.pend;
-    const OptHyper hy{f.kind, f.lr, f.mom, f.b1, f.b2, f.eps};
-    const float lr_t = fly ? opt_lr_t(hy, f.kind == kOptAdam ? *f.iter_prev : 0) : 0.f;
+    const OptHyper hy = f.h;   // a local copy: read through a.fly, three instantiations move SGPR spills
+    const float lr_t = fly ? opt_lr_t(hy, opt_uses_t(hy.kind) ? *f.iter_prev : 0) : 0.f;
     for (int i = tid; i < 10 * CC; i += 256) {
       const bool isb = i >= 9 * CC;
       const int j = isb ? i - 9 * CC : i;
@@ -137,8 +136,8 @@ __global__ __launch_bounds__(256) void cgen_fwd_kernel(GFwdArgs a) {
 #pragma unroll
         for (int r = 1; r < kMaxGrep; ++r) g += gv[r];
         float m = 0.f, v = 0.f;
-        if (f.kind != kOptSGD) m = isb ? f.mbc[j] : f.mwc[j];
-        if (f.kind == kOptAdam) v = isb ? f.vbc[j] : f.vwc[j];
+        if (opt_has_m(hy.kind)) m = isb ? f.mbc[j] : f.mwc[j];
+        if (opt_has_v(hy.kind)) v = isb ? f.vbc[j] : f.vwc[j];
         w = opt_step(hy, lr_t, w, g, m, v);
       }
       wcs[i] = w;
@@ -240,8 +239,7 @@ __global__ __launch_bounds__(256) void cgen_fwd_kernel(GFwdArgs a) {
 // The optimizer of the fused generic step (ops/kernels.py CgenOpt): w / m / v point at the Dense kernel's
 // elements of the flat buffers.
 struct TdeCgenOpt {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float* w; float* m; float* v;
   const long long* iterations;
 };
@@ -249,8 +247,7 @@ struct TdeCgenOpt {
 // Fused step, the backward's head workgroup (ops/kernels.py CgenHead): flat buffers w / m / v, the head's
 // element offsets (off_b1 < 0: no bias), t = *iterations; *pend_set = 1 and *iter_prev = t at the end.
 struct TdeCgenHead {
-  int kind;
-  float lr, mom, b1, b2, eps;
+  tde::OptHyper h;
   float* w; float* m; float* v;
   long long off_w2, off_b2, off_b1;
   const long long* iterations;
@@ -591,16 +588,9 @@ __global__ __launch_bounds__(NW * 64) void cgen_bwd_kernel(GBwdArgs a) {
     if (a.hopt_on) {
       // fused step: the head's update in place, then the previous step's conv update committed
       const TdeCgenHead& o = a.hopt;
-      const OptHyper hy{o.kind, o.lr, o.mom, o.b1, o.b2, o.eps};
       const long long t = *o.iterations;
-      const float lr_t = opt_lr_t(hy, t);
-      auto upd = [&](long long e, float g) {
-        float m = o.kind != kOptSGD ? o.m[e] : 0.f;
-        float v = o.kind == kOptAdam ? o.v[e] : 0.f;
-        o.w[e] = opt_step(hy, lr_t, o.w[e], g, m, v);
-        if (o.kind != kOptSGD) o.m[e] = m;
-        if (o.kind == kOptAdam) o.v[e] = v;
-      };
+      const float lr_t = opt_lr_t(o.h, t);
+      auto upd = [&](long long e, float g) { opt_step_at(o.h, lr_t, o.w, o.m, o.v, e, g); };
 #pragma unroll
       for (int j = 0; j < F::UTW; ++j) {
         const int ut = wave + NW * j;
@@ -638,8 +628,7 @@ __global__ __launch_bounds__(NW * 64) void cgen_bwd_kernel(GBwdArgs a) {
   // copy of the rows this launch read
   if (a.opt_on) {
     const TdeCgenOpt& o = a.opt;
-    const OptHyper hy{o.kind, o.lr, o.mom, o.b1, o.b2, o.eps};
-    const float lr_t = opt_lr_t(hy, o.kind == kOptAdam ? *o.iterations : 0);
+    const float lr_t = opt_lr_t(o.h, opt_uses_t(o.h.kind) ? *o.iterations : 0);
 #pragma unroll
     for (int j = 0; j < F::TW; ++j) {
       const int t = wave + NW * j;
@@ -649,11 +638,7 @@ __global__ __launch_bounds__(NW * 64) void cgen_bwd_kernel(GBwdArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int row = rt * 16 + fq * 4 + r, col = nt * 16 + fr;
           const size_t e = (size_t)(p * CC + row) * HD + col;
-          float m = o.kind != kOptSGD ? o.m[e] : 0.f;
-          float v = o.kind == kOptAdam ? o.v[e] : 0.f;
-          o.w[e] = opt_step(hy, lr_t, W1s[row * F::RG + col], accw[j][r], m, v);
-          if (o.kind != kOptSGD) o.m[e] = m;
-          if (o.kind == kOptAdam) o.v[e] = v;
+          opt_step_at(o.h, lr_t, W1s[row * F::RG + col], o.w, o.m, o.v, e, accw[j][r]);
         }
       }
     }
@@ -811,8 +796,8 @@ TDE_API int tde_cgen_fwd(int CC, int HD, const float* x, const float* wc, const 
                          hipStream_t stream) {
   if (!tde_cgen_supported(CC, HD) || (W & 3) || W > 32 || H < 4 || W < 4 || ((H - 2) & 1) || ((W - 2) & 1))
     return -1;
-  if (fly && (!opt_kind_fused(fly->kind) || !fly->pend || !fly->gwc || !fly->gbc || fly->grep < 1 || fly->grep > kMaxGrep || !fly->iter_prev ||
-              (fly->kind != kOptSGD && (!fly->mwc || !fly->mbc)) || (fly->kind == kOptAdam && (!fly->vwc || !fly->vbc)) ||
+  if (fly && (!opt_kind_fused(fly->h.kind) || !fly->pend || !fly->gwc || !fly->gbc || fly->grep < 1 || fly->grep > kMaxGrep || !fly->iter_prev ||
+              !opt_slots_ok(fly->h.kind, fly->mwc, fly->vwc) || !opt_slots_ok(fly->h.kind, fly->mbc, fly->vbc) ||
               !fly->sw2 || !fly->sb2 || !fly->hsnap || fly->hC < 1 || fly->hC > 16))
     return -3;
   if (!x || !wc || !bc || !W1 || !hpre || !Pt || !amax || (ldPt & 7) || ldPt < B || lda < B || hrep < 1 ||
@@ -839,14 +824,14 @@ TDE_API int tde_cgen_bwd(int CC, int HD, const float* x, const void* amax, int l
                          long long crep_stride, const TdeCgenHead* hopt, const FlatApply* fcommit,
                          const XgPush* push, int B, int H, int W, hipStream_t stream) {
   if (!tde_cgen_supported(CC, HD) || C < 1 || C > 16 || W > 32 || (W & 3)) return -1;
-  if (opt && (!opt_kind_fused(opt->kind) || !opt->w || (opt->kind != kOptSGD && !opt->m) || (opt->kind == kOptAdam && (!opt->v || !opt->iterations))))
+  if (opt && (!opt_kind_fused(opt->h.kind) || !opt->w || !opt_slots_ok(opt->h.kind, opt->m, opt->v) || (opt_uses_t(opt->h.kind) && !opt->iterations)))
     return -3;
   if (crep < 1 || crep > 64 || (crep > 1 && crep_stride < 10LL * CC)) return -4;
   if (push && push->nranks > 0 &&
       (opt || push->nranks > kXgMaxRanks || push->L <= 0 || (push->L & 3) || (push->off & 3) || !push->epoch))
     return -6;
-  if (hopt && (!opt || !fcommit || !opt_kind_fused(hopt->kind) || (fcommit->nr > 0 && !opt_kind_fused(fcommit->h.kind)) || !fcommit->pend || fcommit->grep > kMaxGrep || fcommit->nr > kFlatRanges ||
-               !hopt->w || (hopt->kind != kOptSGD && !hopt->m) || (hopt->kind == kOptAdam && !hopt->v) ||
+  if (hopt && (!opt || !fcommit || !opt_kind_fused(hopt->h.kind) || (fcommit->nr > 0 && !opt_kind_fused(fcommit->h.kind)) || !fcommit->pend || fcommit->grep > kMaxGrep || fcommit->nr > kFlatRanges ||
+               !hopt->w || !opt_slots_ok(hopt->h.kind, hopt->m, hopt->v) ||
                !hopt->iterations || !hopt->pend_set || !hopt->iter_prev))
     return -5;
   if (!x || !amax || !hpre || !hzero || !W2 || !b2 || !labels || !W1 || !Pt || (!dW1 && !opt) || !dwc || !dbc ||
@@ -859,4 +844,11 @@ TDE_API int tde_cgen_bwd(int CC, int HD, const float* x, const void* amax, int l
              crep, crep_stride, hopt ? *hopt : TdeCgenHead{}, hopt != nullptr, fcommit ? *fcommit : FlatApply{},
              push ? *push : XgPush{}, B, H, W};
   TDE_CGEN_DISPATCH(launch_bwd, CC, HD, a, P, stream)
+}
+
+// Sizes of the ctypes-mirrored structs (tests/test_abi.py): out = {TdeCgenFly, TdeCgenOpt, TdeCgenHead}.
+TDE_API int tde_cgen_abi_sizes(long long* out, int n) {
+  const long long s[] = {(long long)sizeof(TdeCgenFly), (long long)sizeof(TdeCgenOpt), (long long)sizeof(TdeCgenHead)};
+  for (int i = 0; i < n && i < 3; ++i) out[i] = s[i];
+  return 3;
 }

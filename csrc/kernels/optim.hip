@@ -31,31 +31,26 @@ struct OptArgs {
   const OptSeg* segs;
   const int4* table;        // per block: {seg, kind(0=1d,1=tile), a, b}
   const long long* iterations;
-  int kind;                 // 0 sgd, 1 momentum, 2 nesterov, 3 adam, 4 rmsprop, 5 rmsprop with momentum
-  float lr, mom, b1, b2, eps, grad_scale;
+  OptHyper h;
+  float grad_scale;
   int zero_grad;
-  const float* lr_ptr;      // optional device-resident lr (schedules)
+  const float* lr_ptr;      // optional device-resident lr (schedules): replaces h.lr
 };
 
 constexpr int kChunk = 2048;
 constexpr int kTileR = 16;  // rows per transposed-shadow tile (tile = kTileR x 64)
 
+// The hyper-parameters in effect (lr_ptr applied) and the step size.
 struct Hyper {
-  float lr, lr_t;
+  OptHyper oh;
+  float lr_t;
 };
 
-// EXT = false: kinds 0..3 (opt_step; the instruction stream these kinds always had).  EXT = true: the RMSprop
-// kinds (opt_step_x), launched for kinds 4 / 5 only: rms is `m`, the momentum accumulator `v` (kind 5 alone
-// reads or writes it).
-template <bool EXT>
-__device__ __forceinline__ bool uses_m(const OptArgs& a) { return EXT ? true : a.kind != 0; }
-template <bool EXT>
-__device__ __forceinline__ bool uses_v(const OptArgs& a) { return EXT ? a.kind == kOptRMSpropMom : a.kind == 3; }
-
+// EXT = false: kinds 0..3 (the instruction stream these kinds always had).  EXT = true: the RMSprop kinds,
+// launched for kinds 4 / 5 only: rms is `m`, the momentum accumulator `v` (kind 5 alone reads or writes it).
 template <bool EXT>
 __device__ __forceinline__ float upd1(const OptArgs& a, float w, float g, float& m, float& v, const Hyper& h) {
-  const OptHyper oh{a.kind, h.lr, a.mom, a.b1, a.b2, a.eps};
-  return EXT ? opt_step_x(oh, h.lr_t, w, g * a.grad_scale, m, v) : opt_step(oh, h.lr_t, w, g * a.grad_scale, m, v);
+  return opt_step<EXT>(h.oh, h.lr_t, w, g * a.grad_scale, m, v);
 }
 
 // Update 4 consecutive elements at flat index i (16-byte aligned).
@@ -64,27 +59,23 @@ __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& 
   float4 w = *reinterpret_cast<float4*>(a.w + i);
   const float4 g = *reinterpret_cast<float4*>(a.g + i);
   float4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
-  if (uses_m<EXT>(a)) m = *reinterpret_cast<float4*>(a.m + i);
-  if (uses_v<EXT>(a)) v = *reinterpret_cast<float4*>(a.v + i);
+  if (opt_has_m<EXT>(a.h.kind)) m = *reinterpret_cast<float4*>(a.m + i);
+  if (opt_has_v<EXT>(a.h.kind)) v = *reinterpret_cast<float4*>(a.v + i);
   w.x = upd1<EXT>(a, w.x, g.x, m.x, v.x, h);
   w.y = upd1<EXT>(a, w.y, g.y, m.y, v.y, h);
   w.z = upd1<EXT>(a, w.z, g.z, m.z, v.z, h);
   w.w = upd1<EXT>(a, w.w, g.w, m.w, v.w, h);
   *reinterpret_cast<float4*>(a.w + i) = w;
   if (a.zero_grad) *reinterpret_cast<float4*>(a.g + i) = float4{0.f, 0.f, 0.f, 0.f};
-  if (uses_m<EXT>(a)) *reinterpret_cast<float4*>(a.m + i) = m;
-  if (uses_v<EXT>(a)) *reinterpret_cast<float4*>(a.v + i) = v;
+  if (opt_has_m<EXT>(a.h.kind)) *reinterpret_cast<float4*>(a.m + i) = m;
+  if (opt_has_v<EXT>(a.h.kind)) *reinterpret_cast<float4*>(a.v + i) = v;
   return w;
 }
 
 template <bool EXT>
 __device__ __forceinline__ float upds(const OptArgs& a, size_t i, const Hyper& h) {
-  float m = uses_m<EXT>(a) ? a.m[i] : 0.f, v = uses_v<EXT>(a) ? a.v[i] : 0.f;
-  const float w = upd1<EXT>(a, a.w[i], a.g[i], m, v, h);
-  a.w[i] = w;
+  const float w = opt_step_at<EXT>(h.oh, h.lr_t, a.w, a.m, a.v, i, a.g[i] * a.grad_scale);
   if (a.zero_grad) a.g[i] = 0.f;
-  if (uses_m<EXT>(a)) a.m[i] = m;
-  if (uses_v<EXT>(a)) a.v[i] = v;
   return w;
 }
 
@@ -93,9 +84,9 @@ __device__ __forceinline__ void optim_apply(const OptArgs a) {
   __shared__ bf16 tile[kTileR][72];
   const int4 ent = a.table[blockIdx.x];
   const OptSeg s = a.segs[ent.x];
-  Hyper h;
-  h.lr = a.lr_ptr ? *a.lr_ptr : a.lr;
-  h.lr_t = opt_lr_t(OptHyper{a.kind, h.lr, a.mom, a.b1, a.b2, a.eps}, a.kind == kOptAdam ? *a.iterations : 0);
+  Hyper h{a.h, 0.f};
+  if (a.lr_ptr) h.oh.lr = *a.lr_ptr;
+  h.lr_t = opt_lr_t(h.oh, opt_uses_t(a.h.kind) ? *a.iterations : 0);
   const int tid = threadIdx.x;
 
   if (ent.y == 0) {
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(256) void flat_apply_kernel(FlatApply f) {
   if (threadIdx.x == 0) go = f.pend ? *f.pend : 1;
   __syncthreads();
   if (!go) return;
-  flat_apply(f, f.h.kind == kOptAdam ? *f.iterations : 0, blockIdx.x * 256 + threadIdx.x, 256 * gridDim.x);
+  flat_apply(f, opt_uses_t(f.h.kind) ? *f.iterations : 0, blockIdx.x * 256 + threadIdx.x, 256 * gridDim.x);
   __syncthreads();
   if (threadIdx.x == 0 && f.pend) *f.pend = 0;
   if (threadIdx.x == 0 && blockIdx.x == 0 && f.count) atomicAdd(f.count, 1ull);
@@ -216,8 +207,8 @@ TDE_API int tde_flat_apply(float* w, float* g, float* m, float* v, const long lo
                            int kind, float lr, float mom, float b1, float b2, float eps, const int* ranges,
                            int nr, int grep, long long grep_stride, unsigned long long* count,
                            hipStream_t stream) {
-  if (!opt_kind_fused(kind)) return -1;   // flat_apply is opt_step: kinds 0..3
-  if (nr < 0 || nr > kFlatRanges || (kind != kOptSGD && !m) || (kind == kOptAdam && (!v || !iterations)))
+  if (!opt_kind_fused(kind)) return -1;   // flat_apply is opt_step<false>: kinds 0..3
+  if (nr < 0 || nr > kFlatRanges || !opt_slots_ok(kind, m, v) || (opt_uses_t(kind) && !iterations))
     return -1;
   FlatApply f{w, g, m, v, iterations, pend, OptHyper{kind, lr, mom, b1, b2, eps}, nr, {0}, {0}, grep, grep_stride, count};
   for (int i = 0; i < nr; ++i) {
@@ -268,11 +259,11 @@ TDE_API int tde_optim_apply(float* w, float* g, float* m, float* v, void* shadow
                             const long long* iterations, int kind, float lr, float mom, float b1,
                             float b2, float eps, float grad_scale, int zero_grad,
                             const float* lr_ptr, hipStream_t stream) {
-  if (!opt_kind_known(kind) || (opt_uses_m(kind) && !m) || (opt_uses_v(kind) && !v)) return -2;
+  if (!opt_kind_known(kind) || !opt_slots_ok(kind, m, v)) return -2;
   if (nblocks <= 0) return 0;
   if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return -1;
   OptArgs a{w, g, m, v, (bf16*)shadow, (const OptSeg*)segs_dev, (const int4*)table_dev,
-            iterations, kind, lr, mom, b1, b2, eps, grad_scale, zero_grad, lr_ptr};
+            iterations, OptHyper{kind, lr, mom, b1, b2, eps}, grad_scale, zero_grad, lr_ptr};
   if (opt_kind_fused(kind)) optim_apply_kernel<<<nblocks, 256, 0, stream>>>(a);
   else optim_apply_ext_kernel<<<nblocks, 256, 0, stream>>>(a);
   TDE_LAUNCH_CHECK();

@@ -1082,28 +1082,16 @@ struct SnWgradArgs {
   OptHyper h;
 };
 
-// EXT = false: gradient store, or the in-step update of kinds 0..3 (opt_step).  EXT = true: the in-step
-// update of the RMSprop kinds (opt_step_x; rms is `m`, the momentum accumulator `v`), launched for kinds
-// 4 / 5 with apply = 1 only, so the other kinds keep the program they had.
+// EXT = false: gradient store, or the in-step update of kinds 0..3.  EXT = true: the in-step update of the
+// RMSprop kinds (rms is `m`, the momentum accumulator `v`), launched for kinds 4 / 5 with apply = 1 only, so
+// the other kinds keep the program they had.
 template <bool EXT>
 __device__ __forceinline__ void sn_commit(const SnWgradArgs& a, int e, float grad, float lr_t) {
-  if (EXT) {
-    float m = a.m[e];
-    float v = a.h.kind == kOptRMSpropMom ? a.v[e] : 0.f;
-    a.w[e] = opt_step_x(a.h, lr_t, a.w[e], grad, m, v);
-    a.m[e] = m;
-    if (a.h.kind == kOptRMSpropMom) a.v[e] = v;
-    return;
-  }
-  if (!a.apply) {
+  if (!EXT && !a.apply) {
     a.g[e] = grad;
     return;
   }
-  float m = a.h.kind != kOptSGD ? a.m[e] : 0.f;
-  float v = a.h.kind == kOptAdam ? a.v[e] : 0.f;
-  a.w[e] = opt_step(a.h, lr_t, a.w[e], grad, m, v);
-  if (a.h.kind != kOptSGD) a.m[e] = m;
-  if (a.h.kind == kOptAdam) a.v[e] = v;
+  opt_step_at<EXT>(a.h, lr_t, a.w, a.m, a.v, e, grad);
 }
 
 template <bool EXT>
@@ -1306,7 +1294,7 @@ TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int 
                                int kind, float lr, float mom, float b1, float b2, float eps, hipStream_t stream) {
   if (nr > 2 * kSnMaxLayers || nd > kSnMaxLayers || B <= 0) return -1;
   if (step && !iterations) return -2;
-  if (apply && (!opt_kind_known(kind) || !iterations || (opt_uses_m(kind) && !m) || (opt_uses_v(kind) && !v))) return -2;
+  if (apply && (!opt_kind_known(kind) || !iterations || !opt_slots_ok(kind, m, v))) return -2;
   if (!apply && !g) return -2;
   SnWgradArgs a{};
   for (int r = 0; r < nr; ++r) a.r[r] = SnRange{ranges[3 * r], ranges[3 * r + 1], ranges[3 * r + 2]};

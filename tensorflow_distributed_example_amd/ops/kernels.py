@@ -19,14 +19,25 @@ _FLAT_RANGES = 4
 
 
 class OptHyper(_ct.Structure):
+    """``OptHyper`` (csrc/include/tde_optim.h): the first member ``h`` of every optimizer struct below."""
     _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
                 ("eps", _ct.c_float)]
 
 
+def opt_hyper(optimizer):
+    hp = optimizer.hparams()
+    return OptHyper(optimizer.kind_id, float(optimizer.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"])
+
+
+def opt_slots(store, optimizer):
+    """(m, v): the optimizer's first and second slot buffer in ``store`` (None where it has none)."""
+    sl = [store.slot(n) for n in optimizer.slot_names()]
+    return (sl + [None, None])[:2]
+
+
 class StepOpt(_ct.Structure):
     """``TdeStepOpt`` (csrc/kernels/convnet.hip): the optimizer of a fused training step."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
-                ("eps", _ct.c_float), ("w", _ct.c_void_p), ("g", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("w", _ct.c_void_p), ("g", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
                 ("iterations", _ct.c_void_p), ("pend", _ct.c_void_p), ("grep", _ct.c_int),
                 ("grep_stride", _ct.c_longlong), ("fly_count", _ct.c_void_p), ("hsrc_w2", _ct.c_void_p),
                 ("hsrc_b2", _ct.c_void_p), ("hsrc_b1", _ct.c_void_p), ("hsnap", _ct.c_void_p), ("hC", _ct.c_int)]
@@ -42,8 +53,7 @@ class FlatApply(_ct.Structure):
 
 class XgApply(_ct.Structure):
     """``TdeXgApply`` (csrc/comm/xgmi_allreduce.hip): the optimizer fused into the all-reduce."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
-                ("eps", _ct.c_float), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
                 ("iterations", _ct.c_void_p), ("sh", _ct.c_void_p), ("sh_lo", _ct.c_longlong), ("sh_hi", _ct.c_longlong),
                 ("sht", _ct.c_void_p), ("sh_cols", _ct.c_int), ("sht_ld", _ct.c_longlong),
                 ("push_lo", _ct.c_longlong), ("push_hi", _ct.c_longlong), ("rep", _ct.c_void_p), ("nrep", _ct.c_int),
@@ -57,10 +67,15 @@ class XgPush(_ct.Structure):
                 ("off", _ct.c_longlong), ("rank", _ct.c_int), ("nranks", _ct.c_int)]
 
 
+class BnOpt(_ct.Structure):
+    """``TdeBnOpt`` (csrc/kernels/bncnn.hip): the optimizer fused into the BN-CNN's reduce launch."""
+    _fields_ = [("h", OptHyper), ("g", _ct.c_void_p), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
+                ("iterations", _ct.c_void_p)]
+
+
 class BwdOpt(_ct.Structure):
     """``TdeBwdOpt`` (csrc/kernels/convnet.hip): the fused-step part of the trunk backward."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float),
-                ("b2", _ct.c_float), ("eps", _ct.c_float), ("w", _ct.c_void_p), ("m", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("w", _ct.c_void_p), ("m", _ct.c_void_p),
                 ("v", _ct.c_void_p), ("off_w1", _ct.c_longlong), ("off_w2", _ct.c_longlong),
                 ("off_b2", _ct.c_longlong), ("off_b1", _ct.c_longlong), ("W1c", _ct.c_void_p),
                 ("ldw1c", _ct.c_int), ("iterations", _ct.c_void_p), ("iter_prev", _ct.c_void_p),
@@ -69,19 +84,16 @@ class BwdOpt(_ct.Structure):
 
 
 def step_opt(optimizer, w, g, m, v, iterations, pend):
-    hp = optimizer.hparams()
-    return StepOpt(optimizer.kind_id, float(optimizer.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"],
-                   _P(w), _P(g), _P(m), _P(v), _P(iterations), _P(pend))
+    return StepOpt(opt_hyper(optimizer), _P(w), _P(g), _P(m), _P(v), _P(iterations), _P(pend))
 
 
 def flat_apply_spec(optimizer, w, g, m, v, iterations, pend, ranges):
     """ranges: [(lo, n), ...] element ranges of the flat buffers (<= 4)."""
     _req(len(ranges) <= _FLAT_RANGES, "flat_apply: at most 4 ranges")
-    hp = optimizer.hparams()
     f = FlatApply()
     f.w, f.g, f.m, f.v = _P(w), _P(g), _P(m), _P(v)
     f.iterations, f.pend = _P(iterations), _P(pend)
-    f.h = OptHyper(optimizer.kind_id, float(optimizer.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"])
+    f.h = opt_hyper(optimizer)
     f.nr = len(ranges)
     for i, (lo, n) in enumerate(ranges):
         f.lo[i], f.n[i] = int(lo), int(n)
@@ -279,16 +291,14 @@ def convnet_bwd(x, amax, hpre, hzero, b1, W2, b2, labels, *, scale, pre_relu, me
 class CgenOpt(_ct.Structure):
     """``TdeCgenOpt`` (csrc/kernels/convnet_gen.hip): the optimizer the generic fused backward applies to the
     Dense kernel rows in place (w / m / v at the Dense kernel's elements of the flat buffers)."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
-                ("eps", _ct.c_float), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
                 ("iterations", _ct.c_void_p)]
 
 
 class CgenFly(_ct.Structure):
     """``TdeCgenFly`` (csrc/kernels/convnet_gen.hip): the generic fused step's forward side — the previous
     step's conv update applied on the fly while ``*pend``, and the head snapshot."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
-                ("eps", _ct.c_float), ("pend", _ct.c_void_p), ("gwc", _ct.c_void_p), ("gbc", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("pend", _ct.c_void_p), ("gwc", _ct.c_void_p), ("gbc", _ct.c_void_p),
                 ("grep", _ct.c_int), ("grep_stride", _ct.c_longlong), ("mwc", _ct.c_void_p), ("mbc", _ct.c_void_p),
                 ("vwc", _ct.c_void_p), ("vbc", _ct.c_void_p), ("iter_prev", _ct.c_void_p), ("sb1", _ct.c_void_p),
                 ("sw2", _ct.c_void_p), ("sb2", _ct.c_void_p), ("hsnap", _ct.c_void_p), ("hC", _ct.c_int)]
@@ -297,8 +307,7 @@ class CgenFly(_ct.Structure):
 class CgenHead(_ct.Structure):
     """``TdeCgenHead`` (csrc/kernels/convnet_gen.hip): the generic fused step's head update in the backward's
     head workgroup (flat buffers + the head's element offsets)."""
-    _fields_ = [("kind", _ct.c_int), ("lr", _ct.c_float), ("mom", _ct.c_float), ("b1", _ct.c_float), ("b2", _ct.c_float),
-                ("eps", _ct.c_float), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
+    _fields_ = [("h", OptHyper), ("w", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
                 ("off_w2", _ct.c_longlong), ("off_b2", _ct.c_longlong), ("off_b1", _ct.c_longlong),
                 ("iterations", _ct.c_void_p), ("pend_set", _ct.c_void_p), ("iter_prev", _ct.c_void_p)]
 

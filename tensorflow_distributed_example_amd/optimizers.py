@@ -43,6 +43,11 @@ class Optimizer:
     def hparams(self):
         return dict(mom=0.0, b1=0.9, b2=0.999, eps=1e-7)
 
+    def key(self):
+        """Everything a kernel argument struct holds of this optimizer: a plan that built its structs at one
+        key rebuilds them when the key has changed (compared for equality only, never stored)."""
+        return (self.kind_id, float(self.learning_rate), tuple(sorted(self.hparams().items())))
+
     def apply_reference(self, w, g, slots, step):
         raise NotImplementedError
 

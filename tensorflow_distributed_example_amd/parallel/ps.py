@@ -27,6 +27,7 @@ import torch
 
 from .. import _native as N
 from .. import backend as Kb
+from ..optimizers import FUSED_KINDS
 from . import cluster as CL
 from . import comm as CM
 from .strategy import Strategy
@@ -202,7 +203,7 @@ class PSClient:
 
     def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7):
         """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms)."""
-        if int(kind) not in (0, 1, 2, 3):
+        if int(kind) not in FUSED_KINDS:
             raise ValueError(f"the parameter server applies optimizer kinds 0..3 only (got kind {kind}; RMSprop "
                              "is not supported under ParameterServerStrategy)")
         for c in self.conns:

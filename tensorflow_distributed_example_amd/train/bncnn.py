@@ -28,6 +28,7 @@ from .. import _native as N
 from .. import backend as Kb
 from ..losses import SparseCategoricalCrossentropy
 from ..models import layers as L
+from ..ops.kernels import BnOpt, opt_hyper, opt_slots
 from .program import OptimizerKernel, ReplicaPlan
 
 BN_NONE, BN_TRAIN, BN_MOVING, BN_BATCH, BN_SAVED = 0, 1, 2, 3, 4
@@ -58,13 +59,6 @@ N.register_hip({
     # B, D, rate, seed, iter, layer_id, out, stream
     "tde_bncnn_dropout_mask": (_i, [_i, _i, C.c_float, C.c_ulonglong, _vp, _i, _vp, _vp]),
 })
-
-
-class BnOpt(C.Structure):
-    """Fused optimizer of the reduce launch (step mode "local")."""
-    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("mom", C.c_float), ("b1", C.c_float), ("b2", C.c_float),
-                ("eps", C.c_float), ("g", C.c_void_p), ("w", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
-                ("iterations", C.c_void_p)]
 
 
 class Geo(C.Structure):
@@ -444,16 +438,11 @@ class BnCnnPlan(ReplicaPlan):
         self._opt_key_set = self._opt_key()
         if mode == "local":
             o, st = self.optimizer, self.store
-            sl = o.slot_names()
-            m = st.slot(sl[0]) if sl else None
-            v = st.slot(sl[1]) if len(sl) > 1 else None
-            hp = o.hparams()
-            self._bnopt = BnOpt(o.kind_id, float(o.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"],
-                                _P(st.g), _P(st.w), _P(m), _P(v), _P(self.iterations))
+            m, v = opt_slots(st, o)
+            self._bnopt = BnOpt(opt_hyper(o), _P(st.g), _P(st.w), _P(m), _P(v), _P(self.iterations))
 
     def _opt_key(self):
-        o = self.optimizer
-        return (o.kind_id, float(o.learning_rate), tuple(sorted(o.hparams().items()))) if o is not None else None
+        return self.optimizer.key() if self.optimizer is not None else None
 
     def refresh(self):
         # the launch descriptor carries lr / hyper-parameters by value

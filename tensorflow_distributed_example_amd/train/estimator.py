@@ -378,9 +378,9 @@ class Estimator:
             m._require_built()
             shapes = {n: tuple(m._store.segments[n].shape) for n in m._store.order}
             self._psc = strategy.client(shapes)
-            from ..optimizers import KIND
             hp = m.optimizer.hparams()
-            self._psc.set_optimizer(m.optimizer.kind_id, hp["mom"], hp["b1"], hp["b2"], hp["eps"])
+            self._psc.set_optimizer(m.optimizer.kind_id, momentum=hp["mom"], beta1=hp["b1"], beta2=hp["b2"],
+                                    epsilon=hp["eps"])
         return self._psc
 
     def _train_ps(self, strategy, input_fn, hooks, steps, max_steps, saving_listeners):

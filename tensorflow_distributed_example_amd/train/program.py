@@ -268,14 +268,12 @@ class OptimizerKernel:
     def apply(self, zero_grad=True):
         N = self.N
         st = self.store
-        opt = self.optimizer
-        hp = opt.hparams()
-        m = st.slot(opt.slot_names()[0]) if opt.slot_names() else None
-        v = st.slot(opt.slot_names()[1]) if len(opt.slot_names()) > 1 else None
+        from ..ops.kernels import opt_hyper, opt_slots
+        h = opt_hyper(self.optimizer)
+        m, v = opt_slots(st, self.optimizer)
         rc = N.hip().tde_optim_apply(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v), self.shadow.data_ptr(),
                                      self.segs_dev.data_ptr(), self.table_dev.data_ptr(), self.nblocks,
-                                     self.iterations.data_ptr(), opt.kind_id,
-                                     float(opt.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"], 1.0,
+                                     self.iterations.data_ptr(), h.kind, h.lr, h.mom, h.b1, h.b2, h.eps, 1.0,
                                      int(zero_grad), None, N.stream_ptr())
         N.check(rc, "tde_optim_apply")
 
@@ -285,18 +283,15 @@ def f32_xg_apply_spec(plan):
     all-reduce applies the optimizer to ``store.w`` / slots (step mode "xgmi")."""
     from ..ops import kernels as K
     st, opt = plan.store, plan.optimizer
-    sl = opt.slot_names()
-    m = st.slot(sl[0]) if sl else None
-    v = st.slot(sl[1]) if len(sl) > 1 else None
-    hp = opt.hparams()
+    m, v = K.opt_slots(st, opt)
     # the plan's step pushed part of the bucket into the owners itself (fused exchange; a replica without
     # data this step pushed nothing)
     lo, hi = plan.push_range() if (getattr(plan, "_push", None) is not None and getattr(plan, "_pushed", False)) \
         else (0, 0)
     if hasattr(plan, "_pushed"):
         plan._pushed = False
-    return K.XgApply(opt.kind_id, float(opt.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"],
-                     K._P(st.w), K._P(m), K._P(v), K._P(plan.iterations), None, 0, 0, None, 0, 0, lo, hi)
+    return K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(plan.iterations), None, 0, 0, None, 0, 0,
+                     lo, hi)
 
 
 def match_convnet(model, loss):
@@ -511,17 +506,13 @@ class ConvNetPlan(ReplicaPlan):
         if mode == "plain":
             return
         K, st, opt = self.K, self.store, self.optimizer
-        sl = opt.slot_names()
-        m = st.slot(sl[0]) if sl else None
-        v = st.slot(sl[1]) if len(sl) > 1 else None
-        self._slots = (m, v)
-        self._opt_key_set = self._opt_key()
+        self._slots = m, v = K.opt_slots(st, opt)
+        self._opt_key_set = opt.key()
         if mode != "local":
             return
         seg = st.segments
         conv = [(seg[self.names["wc"]].offset, seg[self.names["wc"]].numel),
                 (seg[self.names["bc"]].offset, seg[self.names["bc"]].numel)]
-        hp = opt.hparams()
         P_ = K._P
         self._fopt, self._bopt, self._flush = [], [], []
         for q in (0, 1):
@@ -540,8 +531,8 @@ class ConvNetPlan(ReplicaPlan):
             commit.count = self.ucount[0].data_ptr()
             b1 = self.names["b1"]
             self._bopt.append(K.BwdOpt(
-                opt.kind_id, float(opt.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"], P_(st.w), P_(m),
-                P_(v), seg[self.names["w1"]].offset, seg[self.names["w2"]].offset, seg[self.names["b2"]].offset,
+                K.opt_hyper(opt), P_(st.w), P_(m), P_(v),
+                seg[self.names["w1"]].offset, seg[self.names["w2"]].offset, seg[self.names["b2"]].offset,
                 seg[b1].offset if b1 is not None else -1, P_(self.W1col),
                 self.W1col.stride(0) if self.W1col is not None else 0, P_(self.iterations), P_(self.iter_prev),
                 commit, self.pend[q].data_ptr(), self.crep, self._conv_span))
@@ -566,36 +557,30 @@ class ConvNetPlan(ReplicaPlan):
             raise ValueError("the fused exchange needs step mode 'xgmi' and the float32 plan")
         self._push = spec
 
-    def _opt_key(self):
-        o = self.optimizer
-        return (o.kind_id, float(o.learning_rate), tuple(sorted(o.hparams().items())))
-
     def refresh(self):
         # the kernel argument structs carry lr / hyper-parameters by value
-        if self.step_mode != "plain" and self._opt_key_set != self._opt_key():
+        if self.step_mode != "plain" and self._opt_key_set != self.optimizer.key():
             self.set_step_mode(self.step_mode)
 
     def xg_apply_spec(self):
         """``XgApply`` for the communicator's fused all-reduce (step mode "xgmi")."""
         st, opt = self.store, self.optimizer
         m, v = self._slots
-        hp = opt.hparams()
         seg = st.segments[self.names["w1"]]
         K = self.K
         if self.f32:   # no shadow: the all-reduce updates the f32 master weights only
             # the step's backward pushed dW1 itself (a replica without data this step pushed nothing)
             lo, hi = self.push_range() if (self._push is not None and self._pushed) else (0, 0)
             self._pushed = False
-            spec = K.XgApply(opt.kind_id, float(opt.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"],
-                             K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), None, 0, 0, None, 0, 0, lo, hi)
+            spec = K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), None, 0, 0, None,
+                             0, 0, lo, hi)
             if self._xg_rep:   # the conv gradients wait in the replicas of parity 0
                 spec.rep, spec.nrep = self.gconv[0].data_ptr(), self.crep
                 spec.rep_lo, spec.rep_hi = self._conv_lo, self._conv_lo + self._conv_span
                 spec.rep_stride = self._conv_span
             return spec
-        return K.XgApply(opt.kind_id, float(opt.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"],
-                         K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), K._P(self.W1row), seg.offset,
-                         seg.offset + seg.numel, K._P(self.W1col), self.Hd,
+        return K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), K._P(self.W1row),
+                         seg.offset, seg.offset + seg.numel, K._P(self.W1col), self.Hd,
                          self.W1col.stride(0) if self.W1col is not None else 0)
 
     def finish(self):
@@ -807,49 +792,40 @@ class ConvNetGenPlan(ReplicaPlan):
         if mode != "local":
             return
         K, st, o = self.K, self.store, self.optimizer
-        sl = o.slot_names()
-        m = st.slot(sl[0]) if sl else None
-        v = st.slot(sl[1]) if len(sl) > 1 else None
-        hp = o.hparams()
+        m, v = K.opt_slots(st, o)
+        h = K.opt_hyper(o)
         seg = st.segments
         at = lambda t, name: None if t is None or name is None else t.data_ptr() + 4 * seg[self.names[name]].offset  # noqa: E731
-        kind, lr = o.kind_id, float(o.learning_rate)
-        self._copt = K.CgenOpt(kind, lr, hp["mom"], hp["b1"], hp["b2"], hp["eps"], at(st.w, "w1"), at(m, "w1"),
-                               at(v, "w1"), self.iterations.data_ptr())
+        self._copt = K.CgenOpt(h, at(st.w, "w1"), at(m, "w1"), at(v, "w1"), self.iterations.data_ptr())
         conv = [(self._conv_lo, self._conv_span)]
         self._fly, self._hopt, self._commit, self._flush = [], [], [], []
         for q in (0, 1):
             # forward of parity q: the update of the previous step (set 1-q) on the fly, the head snapshot
             self._fly.append(K.CgenFly(
-                kind, lr, hp["mom"], hp["b1"], hp["b2"], hp["eps"], self.pend[1 - q].data_ptr(),
-                self._gset(1 - q, "wc").data_ptr(), self._gset(1 - q, "bc").data_ptr(), self.crep, self._conv_span,
-                at(m, "wc"), at(m, "bc"), at(v, "wc"), at(v, "bc"), self.iter_prev.data_ptr(),
-                at(st.w, "b1"), at(st.w, "w2"), at(st.w, "b2"), self.hsnap.data_ptr(), self.Cls))
+                h, self.pend[1 - q].data_ptr(), self._gset(1 - q, "wc").data_ptr(),
+                self._gset(1 - q, "bc").data_ptr(), self.crep, self._conv_span, at(m, "wc"), at(m, "bc"), at(v, "wc"),
+                at(v, "bc"), self.iter_prev.data_ptr(), at(st.w, "b1"), at(st.w, "w2"), at(st.w, "b2"), self.hsnap.data_ptr(), self.Cls))
             # backward of parity q: the head in place, the previous step's conv update committed, set q flagged
             b1 = self.names["b1"]
             self._hopt.append(K.CgenHead(
-                kind, lr, hp["mom"], hp["b1"], hp["b2"], hp["eps"], st.w.data_ptr(), K._P(m), K._P(v),
-                seg[self.names["w2"]].offset, seg[self.names["b2"]].offset, seg[b1].offset if b1 is not None else -1,
-                self.iterations.data_ptr(), self.pend[q].data_ptr(), self.iter_prev.data_ptr()))
+                h, st.w.data_ptr(), K._P(m), K._P(v), seg[self.names["w2"]].offset, seg[self.names["b2"]].offset,
+                seg[b1].offset if b1 is not None else -1, self.iterations.data_ptr(), self.pend[q].data_ptr(),
+                self.iter_prev.data_ptr()))
             for lst, qq in ((self._commit, 1 - q), (self._flush, q)):
                 f = K.flat_apply_spec(o, st.w, None, m, v, self.iterations, self.pend[qq], conv)
                 f.g = self.gconv[qq].data_ptr() - 4 * self._conv_lo   # indexed with the flat offsets
                 f.grep, f.grep_stride = self.crep, self._conv_span
                 lst.append(f)
-        self._opt_key_set = self._opt_key()
+        self._opt_key_set = o.key()
 
     def finish(self):
         if self.step_mode == "local":
             # only the last step's conv update can be pending (each backward commits the previous one)
             self.K.flat_apply(self._flush[1 - self.parity])
 
-    def _opt_key(self):
-        o = self.optimizer
-        return (o.kind_id, float(o.learning_rate), tuple(sorted(o.hparams().items())))
-
     def refresh(self):
         # the launch descriptors carry lr / hyper-parameters by value
-        if self.step_mode == "local" and self._opt_key_set != self._opt_key():
+        if self.step_mode == "local" and self._opt_key_set != self.optimizer.key():
             self.set_step_mode("local")
 
     def push_range(self):

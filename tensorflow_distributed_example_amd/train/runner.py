@@ -459,10 +459,6 @@ class Program:
                     torch.cuda.synchronize(d)
             self._comm_warm = True
 
-    def _key(self):
-        o = self.model.optimizer
-        return (float(o.learning_rate), o.kind, tuple(sorted(o.hparams().items())))
-
     def _parities(self):
         return tuple(p.parity for p in self.plans)
 
@@ -496,7 +492,7 @@ class Program:
                 for p, q in zip(self.plans, start):
                     p.parity = q
             self.graphs[start] = (gs, self._end)
-            self._graph_key = self._key()
+            self._graph_key = self.model.optimizer.key()
             self.graph = gs[0]
             return
         dev = self.devices[0]
@@ -517,12 +513,12 @@ class Program:
                     p.parity = q
             torch.cuda.synchronize(dev)
         self.graphs[start] = (g, self._end)
-        self._graph_key = self._key()
+        self._graph_key = self.model.optimizer.key()
         self.graph = g
 
     def run(self):
         if self.use_graph:
-            if self._graph_key != self._key():
+            if self._graph_key != self.model.optimizer.key():
                 self.graphs = {}
             if self._parities() not in self.graphs:
                 try:

@@ -39,6 +39,7 @@ import torch
 from .. import _native as N
 from ..losses import SparseCategoricalCrossentropy
 from ..models import layers as L
+from ..ops.kernels import OptHyper, opt_hyper, opt_slots
 from .elementwise_ids import dropout_ids
 from .program import OptimizerKernel, ReplicaPlan
 
@@ -306,19 +307,13 @@ class SmallNetPlan(ReplicaPlan):
         self._step(0, x, y, B)
         local = self.step_mode == "local"
         st, opt = self.store, self.optimizer
-        m = v = None
-        kind, lr, hp = 0, 0.0, dict(mom=0.0, b1=0.0, b2=0.0, eps=0.0)
-        if local:
-            sl = opt.slot_names()
-            m = st.slot(sl[0]) if sl else None
-            v = st.slot(sl[1]) if len(sl) > 1 else None
-            kind, lr, hp = opt.kind_id, float(opt.learning_rate), opt.hparams()
+        m, v = opt_slots(st, opt) if local else (None, None)
+        h = opt_hyper(opt) if local else OptHyper()
         rc = self.lib.tde_smallnet_wgrad(
             self.ranges.ctypes.data, self.nranges, self.dense.ctypes.data, len(self.dense), self.conv_nblk, B,
             self.part.data_ptr(), self.npart, self.rec.data_ptr(), self.nrec, st.w.data_ptr(), st.g.data_ptr(),
             N.ptr(m), N.ptr(v), self.iterations.data_ptr(), N.ptr(self.step_word), self.metrics.data_ptr(), int(local),
-            kind, lr,
-            hp["mom"], hp["b1"], hp["b2"], hp["eps"], N.stream_ptr())
+            h.kind, h.lr, h.mom, h.b1, h.b2, h.eps, N.stream_ptr())
         N.check(rc, "tde_smallnet_wgrad")
 
     def apply(self):

@@ -254,8 +254,7 @@ for name, opt in opts.items():
     opt.apply_reference(rw, gsum, slots, 2)   # Adam t = step + 1 = 3 = iterations
     sh = torch.zeros(rows * cols, dtype=torch.bfloat16, device="cuda")
     sht = torch.zeros(cols, rows, dtype=torch.bfloat16, device="cuda")
-    hp = opt.hparams()
-    spec = K.XgApply(opt.kind_id, opt.learning_rate, hp["mom"], hp["b1"], hp["b2"], hp["eps"], w.data_ptr(),
+    spec = K.XgApply(K.opt_hyper(opt), w.data_ptr(),
                      K._P(m), K._P(v), it.data_ptr(), sh.data_ptr(), lo, lo + rows * cols, sht.data_ptr(), cols,
                      rows)
     gb = grads[rank].clone()
