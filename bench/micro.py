@@ -100,7 +100,7 @@ def main():
     def k_bwd(stamps=None):
         q = plan.parity
         local = plan.step_mode == "local"
-        dwc, dbc = plan._gconv_views(q) if local else (plan._g("wc"), plan._g("bc"))
+        dwc, dbc, _ = plan._conv_grads(q)
         K.convnet_bwd(x, plan.amax, plan.hpre2[q], plan.hpre2[1 - q], plan._v("b1"), plan._v("w2"), plan._v("b2"), y,
                       scale=plan.scale, pre_relu=True, metrics=plan.metrics, W1row=plan.W1row, Pt=plan.Pt,
                       dW1=plan._g("w1"), dwc=dwc, dbc=dbc, dW2=plan._g("w2"), db2=plan._g("b2"), db1=plan._g("b1"),

@@ -157,6 +157,7 @@ def match_bncnn(model, loss):
 
 class BnCnnPlan(ReplicaPlan):
     kind = "fused_bncnn"
+    hyper_by_value = ("local",)   # BnOpt
     compute_dtype = "fp32"
     input_dtype = torch.float32
 
@@ -237,9 +238,6 @@ class BnCnnPlan(ReplicaPlan):
         self.x_stride = H0 * W0 * C0
         self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
         self._bn_segs = self._bn_gradient_segments()
-        self._opt_key_set = None
-        self._push = None     # fused DP exchange (step mode "xgmi", set_push)
-        self._pushed = False
 
     def head_fold_ok(self, B):
         """TDE_BNCNN_HEAD_FOLD=1: the training head runs inside the dense backward launch (one launch fewer per
@@ -416,38 +414,18 @@ class BnCnnPlan(ReplicaPlan):
         return mode == "local" and self._opt_fused() and self.device.type == "cuda" and \
             self._bn_segs is not None
 
-    def xg_apply_spec(self):
-        from .program import f32_xg_apply_spec
-        return f32_xg_apply_spec(self)
-
     def push_range(self):
         """Bucket range the reduce launch can push into the xGMI owners itself: the Dense(200) kernel's
         gradient (94 % of Model B's gradient bytes)."""
         seg = self.store.segments[f"{self.dense.name}/kernel"]
         return seg.offset, seg.offset + seg.numel
 
-    def set_push(self, spec):
-        if spec is not None and self.step_mode != "xgmi":
-            raise ValueError("the fused exchange needs step mode 'xgmi'")
-        self._push = spec
-
     def set_step_mode(self, mode):
         super().set_step_mode(mode)
-        if mode != "xgmi":
-            self._push = None
-        self._opt_key_set = self._opt_key()
         if mode == "local":
             o, st = self.optimizer, self.store
             m, v = opt_slots(st, o)
             self._bnopt = BnOpt(opt_hyper(o), _P(st.g), _P(st.w), _P(m), _P(v), _P(self.iterations))
-
-    def _opt_key(self):
-        return self.optimizer.key() if self.optimizer is not None else None
-
-    def refresh(self):
-        # the launch descriptor carries lr / hyper-parameters by value
-        if self.step_mode == "local" and self._opt_key_set != self._opt_key():
-            self.set_step_mode("local")
 
     def _bn_gradient_segments(self):
         """(part, out, len, 1) of every BN gamma / beta gradient (the backward writes them into the bucket),

@@ -418,7 +418,7 @@ class LayerwisePlan(PG.ReplicaPlan):
     def predict(self, x, B=None):
         B = self.B if B is None else B
         self._input(x, B)
-        self._labels = self._zero_labels(B)
+        self._labels = self._dummy_labels(B)
         tr = Kb.resolve_training(False)
         for st in self.stages:
             st.fwd(self, B, tr, mode="predict")
@@ -430,11 +430,6 @@ class LayerwisePlan(PG.ReplicaPlan):
         for st in self.stages:
             if getattr(st, "colstats", None) is not None:
                 st.colstats.zero_()
-
-    def _zero_labels(self, B):
-        if not hasattr(self, "_zl") or self._zl.shape[0] < B:
-            self._zl = torch.zeros(max(B, self.B), dtype=torch.int32, device=self.device)
-        return self._zl
 
 
 # ---------------------------------------------------------------------------------------

@@ -53,6 +53,12 @@ class ReplicaPlan:
         self.iterations = torch.zeros(1, dtype=torch.int64, device=self.device)
         for s in optimizer.slot_names() if optimizer is not None else []:
             store.slot(s)
+        # step mode "xgmi" with the fused exchange (set_push): the step stores its big weight gradient straight
+        # into the xGMI owners' contribution areas; _pushed marks that the step's launch did so (xg_apply_spec)
+        self._push = None
+        self._pushed = False
+        self._opt_key_set = None   # optimizer.key() the descriptors of the current step mode were built at
+        self._zl = None
 
     def reset_metrics(self):
         self.metrics.zero_()
@@ -85,6 +91,9 @@ class ReplicaPlan:
     compute_dtype = "fp32"        # what the plan's kernels compute in ("fp32" | "bf16"; bench / logs)
     parity = 0   # step parity of plans that double-buffer across steps (one hipGraph per start parity)
 
+    # step modes whose launch descriptors carry the optimizer's hyper-parameters by value (``refresh``)
+    hyper_by_value = ()
+
     def supports_step_mode(self, mode):
         return mode == "plain"
 
@@ -98,6 +107,42 @@ class ReplicaPlan:
         if not self.supports_step_mode(mode):
             raise ValueError(f"{self.kind} plan does not support step mode {mode!r}")
         self.step_mode = mode
+        if mode != "xgmi":
+            self._push = None
+        self._opt_key_set = self._opt_key()
+
+    def _opt_key(self):
+        return self.optimizer.key() if self.optimizer is not None else None
+
+    def push_range(self):
+        """Bucket range the step can push into the xGMI owners itself, or None when this plan cannot."""
+        return None
+
+    def set_push(self, spec):
+        """Fused data-parallel exchange (step mode "xgmi"): ``spec`` is the communicator's ``XgPush`` for
+        this replica (None: the whole bucket stays local, the all-reduce pushes it)."""
+        if spec is not None and (self.step_mode != "xgmi" or self.push_range() is None):
+            raise ValueError("the fused exchange needs step mode 'xgmi' and the float32 plan")
+        self._push = spec
+
+    def xg_apply_spec(self):
+        """``XgApply`` for the communicator's fused all-reduce (step mode "xgmi") of a plan whose weights are
+        the f32 master store only (no bf16 shadows): it applies the optimizer to ``store.w`` / slots."""
+        from ..ops import kernels as K
+        st, opt = self.store, self.optimizer
+        m, v = K.opt_slots(st, opt)
+        # the plan's step pushed part of the bucket into the owners itself (a replica without data this step
+        # pushed nothing)
+        lo, hi = self.push_range() if (self._push is not None and self._pushed) else (0, 0)
+        self._pushed = False
+        return K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), None, 0, 0, None,
+                         0, 0, lo, hi)
+
+    def _dummy_labels(self, B):
+        """int32 zeros for launches that take labels they do not use (predict)."""
+        if self._zl is None or self._zl.shape[0] < B:
+            self._zl = torch.zeros(max(B, self.B), dtype=torch.int32, device=self.device)
+        return self._zl
 
     @property
     def applies_in_step(self):
@@ -112,6 +157,8 @@ class ReplicaPlan:
 
     def refresh(self):
         """Before an execution is launched or captured: pick up optimizer hyper-parameter changes."""
+        if self.step_mode in self.hyper_by_value and self._opt_key_set != self._opt_key():
+            self.set_step_mode(self.step_mode)
 
 
 # ---------------------------------------------------------------------------------------
@@ -278,22 +325,6 @@ class OptimizerKernel:
         N.check(rc, "tde_optim_apply")
 
 
-def f32_xg_apply_spec(plan):
-    """``XgApply`` of a plan whose weights are the f32 master store only (no bf16 shadows): the xGMI
-    all-reduce applies the optimizer to ``store.w`` / slots (step mode "xgmi")."""
-    from ..ops import kernels as K
-    st, opt = plan.store, plan.optimizer
-    m, v = K.opt_slots(st, opt)
-    # the plan's step pushed part of the bucket into the owners itself (fused exchange; a replica without
-    # data this step pushed nothing)
-    lo, hi = plan.push_range() if (getattr(plan, "_push", None) is not None and getattr(plan, "_pushed", False)) \
-        else (0, 0)
-    if hasattr(plan, "_pushed"):
-        plan._pushed = False
-    return K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(plan.iterations), None, 0, 0, None, 0, 0,
-                     lo, hi)
-
-
 def match_convnet(model, loss):
     """Pattern of the DWK/TF2M small CNN: Conv2D(3x3,relu,bias) on 1 channel ·
     MaxPooling2D(2) · Flatten · Dense(bias[,relu]) · Dense(bias[,softmax]) + SCCE."""
@@ -359,7 +390,187 @@ def gen_fits(filters, units):
     return lds <= 160 * 1024
 
 
-class ConvNetPlan(ReplicaPlan):
+def _env_count(name, default):
+    """A replica count from the environment, 1..8."""
+    return max(1, min(8, int(os.environ.get(name, str(default)))))
+
+
+class SmallCnnPlan(ReplicaPlan):
+    """What the two fused small-CNN plans share: the variables by role, the geometry, and the state of the
+    two-launch step around the launches themselves —
+
+      hpre2   the big Dense's pre-activation by step parity, ``hrep`` split-K replicas each (the forward's
+              adders per address spread out, the consumers sum them; TDE_CONVNET_HREP), and ``hpre`` for
+              eval / predict
+      gconv   the conv gradients by step parity, ``crep`` replicas of the conv segments' span each (backward
+              workgroup x adds into replica x % crep: same-address float atomics from every workgroup
+              serialise at the memory side; TDE_CONVNET_GREP).  Step mode "local": the deferred update of
+              step t (``pend`` flags it, ``iter_prev`` is its step count) is applied on the fly by forward
+              t+1, committed by backward t+1 and flushed by ``finish()``; "xgmi": the all-reduce sums the
+              replicas of set 0 (``_xg_rep``); "plain" adds into the gradient bucket
+      hsnap   the head variables as of the step's forward ([b1 | W2 | b2], written by the forward): the
+              backward's trunk reads them while its head workgroup updates the originals
+
+    A subclass supplies the launches and their descriptors (``set_step_mode``, ``train_step``,
+    ``_infer_forward``) and, where it differs, ``_size_replicas`` and ``_conv_ranges``."""
+    _commit_count = None   # device counter of committed conv updates, where the plan keeps one
+
+    def __init__(self, model, store, device, batch, global_batch, optimizer, pattern):
+        super().__init__(model, store, device, batch, global_batch, optimizer)
+        from ..ops import kernels as K
+        self.K = K
+        c, d1, d2 = pattern["conv"], pattern["dense1"], pattern["dense2"]
+        self.H, self.W, self.C = c.input_shape[0], c.input_shape[1], c.filters
+        self.P = ((self.H - 2) // 2) * ((self.W - 2) // 2)
+        self.Hd, self.Cls = d1.units, d2.units
+        self.pre_relu = d1.activation == "relu"
+        self.logits_out = d2.activation is None
+        n = lambda l, w: f"{l.name}/{w}"  # noqa: E731
+        self.names = dict(wc=n(c, "kernel"), bc=n(c, "bias"), w1=n(d1, "kernel"),
+                          b1=n(d1, "bias") if d1.use_bias else None, w2=n(d2, "kernel"), b2=n(d2, "bias"))
+        seg = store.segments
+        sw, sb = seg[self.names["wc"]], seg[self.names["bc"]]
+        self._conv_lo = min(sw.offset, sb.offset)
+        self._conv_span = max(sw.offset + sw.numel, sb.offset + sb.numel) - self._conv_lo
+        foreign = any(nm not in (self.names["wc"], self.names["bc"]) and
+                      self._conv_lo <= seg[nm].offset < self._conv_lo + self._conv_span for nm in store.order)
+        self.hrep, self.crep = _env_count("TDE_CONVNET_HREP", 4), _env_count("TDE_CONVNET_GREP", 8)
+        self._size_replicas(foreign)
+        B, dev, Hd, C_ = self.B, self.device, self.Hd, self.Cls
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.hpre2 = torch.zeros(2, self.hrep, B, Hd, **f32)
+        self.hpre = torch.zeros(B, Hd, **f32)
+        self.probs = torch.zeros(B, C_, **f32)
+        self.parity = 0
+        self.gconv = torch.zeros(2, self.crep, self._conv_span, **f32)
+        self.pend = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.iter_prev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.hsnap = torch.zeros(Hd + Hd * C_ + C_, **f32)
+        self._hs_b1 = self.hsnap[:Hd]
+        self._hs_w2 = self.hsnap[Hd: Hd + Hd * C_].view(Hd, C_)
+        self._hs_b2 = self.hsnap[Hd + Hd * C_:]
+        self._flush = None
+
+    def _size_replicas(self, foreign):
+        """Settle ``hrep`` / ``crep`` (preset from the environment) and ``_xg_rep``: whether the xGMI all-reduce
+        takes the conv gradients from the replicas of set 0.  ``foreign``: another variable's segment lies
+        inside the conv span, so a range over the span would cover it too."""
+        raise NotImplementedError
+
+    def supports_step_mode(self, mode):
+        if mode == "plain":
+            return True
+        return self._opt_fused() and self.device.type == "cuda" and mode in ("local", "xgmi")
+
+    def _v(self, key):
+        nm = self.names[key]
+        return None if nm is None else self.store.view(nm)
+
+    def _g(self, key):
+        nm = self.names[key]
+        return None if nm is None else self.store.grad(nm)
+
+    # ------------------------------------------------------------------ the conv-gradient sets
+    def _gset(self, q, key):
+        """Replica 0 of conv variable ``key``'s gradient in parity set q."""
+        sg = self.store.segments[self.names[key]]
+        lo = sg.offset - self._conv_lo
+        return self.gconv[q, 0, lo: lo + sg.numel].view(sg.shape)
+
+    def _gbase(self, q):
+        """Pointer that indexes parity set q's replica 0 with the flat-buffer offsets."""
+        return self.gconv[q].data_ptr() - 4 * self._conv_lo
+
+    def _reads_set(self, spec, q):
+        """Point an update descriptor (``g`` / ``grep`` / ``grep_stride``) at the replicas of parity set q."""
+        spec.g = self._gbase(q)
+        spec.grep, spec.grep_stride = self.crep, self._conv_span
+        return spec
+
+    def _conv_ranges(self):
+        """[(lo, n), ...] of the flat buffers that the commit / flush launches update."""
+        return [(self._conv_lo, self._conv_span)]
+
+    def _conv_apply(self, q, m, v):
+        """``FlatApply`` of the deferred conv update waiting in parity set q (the commit and the flush)."""
+        f = self.K.flat_apply_spec(self.optimizer, self.store.w, None, m, v, self.iterations, self.pend[q],
+                                   self._conv_ranges())
+        f.count = self.K._P(self._commit_count)
+        return self._reads_set(f, q)
+
+    def _conv_grads(self, q):
+        """(dwc, dbc, sets) the backward of parity q adds the conv gradients into; ``sets``: replica 0 of a
+        parity set (the launch spreads its workgroups over the ``crep`` replicas), not the gradient bucket."""
+        if self.step_mode == "local":
+            return self._gset(q, "wc"), self._gset(q, "bc"), True
+        if self.step_mode == "xgmi" and self._xg_rep:
+            return self._gset(0, "wc"), self._gset(0, "bc"), True
+        return self._g("wc"), self._g("bc"), False
+
+    def _head_vars(self):
+        """(b1, W2, b2) the backward's trunk reads: in the fused step the forward's snapshot (the head workgroup
+        updates the originals)."""
+        if self.step_mode == "local":
+            return (self._hs_b1 if self.names["b1"] is not None else None), self._hs_w2, self._hs_b2
+        return self._v("b1"), self._v("w2"), self._v("b2")
+
+    # ------------------------------------------------------------------ plan interface
+    def push_range(self):
+        """Bucket range the backward can push into the xGMI owners itself: the big Dense kernel's gradient
+        (the reference's Dense(64): 99.7 % of the gradient bytes)."""
+        seg = self.store.segments[self.names["w1"]]
+        return seg.offset, seg.offset + seg.numel
+
+    def xg_apply_spec(self):
+        spec = super().xg_apply_spec()
+        if self._xg_rep:   # the conv gradients wait in the replicas of set 0: the all-reduce sums (and zeroes) them
+            spec.rep, spec.nrep = self.gconv[0].data_ptr(), self.crep
+            spec.rep_lo, spec.rep_hi = self._conv_lo, self._conv_lo + self._conv_span
+            spec.rep_stride = self._conv_span
+        return spec
+
+    def finish(self):
+        if self.step_mode == "local":
+            # only the last step's conv update can be pending (each backward commits the previous one)
+            self.K.flat_apply(self._flush[1 - self.parity])
+
+    def step_invariants(self):
+        """The deferred conv update's state between executions (step mode "local"; synchronises): nothing
+        pending, every gradient replica consumed."""
+        torch.cuda.synchronize(self.device)
+        return dict(pending=[int(v) for v in self.pend.cpu()], gconv_abs_max=float(self.gconv.abs().max()))
+
+    def on_weights_loaded(self):
+        # loaded weights replace whatever update was outstanding
+        self.pend.zero_()
+        self.gconv.zero_()
+        self.store.g.zero_()
+
+    def apply(self):
+        # step mode "plain": multi-tensor optimizer (+ grad zeroing + bf16 shadow refresh)
+        self.opt.apply()
+
+    def _infer_forward(self, x, B):
+        """The forward outside training: the Dense pre-activation of x[:B] into ``hpre``."""
+        raise NotImplementedError
+
+    def _infer_head(self, B, labels, scale, **kw):
+        self.K.head_xent(self.hpre, self._v("w2"), self._v("b2"), labels, B=B, scale=scale, pre_bias=self._v("b1"),
+                         pre_relu=self.pre_relu, compute_grad=False, zero_hin=True, **kw)
+
+    def eval_step(self, x, y, B=None):
+        B = self.B if B is None else B
+        self._infer_forward(x, B)
+        self._infer_head(B, y, self.scale, metrics=self.metrics)
+
+    def predict(self, x, B=None):
+        B = self.B if B is None else B
+        self._infer_forward(x, B)
+        self._infer_head(B, self._dummy_labels(B), 1.0, probs=self.probs, probs_are_logits=self.logits_out)
+        return self.probs[:B]
+
+
+class ConvNetPlan(SmallCnnPlan):
     """The DWK/TF2M small CNN as two HIP launches per training step, in the precision of the global
     policy: float32 (the reference's; csrc/kernels/convnet_f32.hip, exact-f32 MFMA over the f32 master
     weights) or mixed_bfloat16 (csrc/kernels/convnet.hip, bf16 MFMA over bf16 weight shadows):
@@ -376,47 +587,24 @@ class ConvNetPlan(ReplicaPlan):
     the Program captures one hipGraph per starting parity."""
     kind = "fused_convnet"
 
+    hyper_by_value = ("local", "xgmi")   # "xgmi": set_step_mode also caches ``_slots`` for xg_apply_spec
+    _mode_set = None
+
     def __init__(self, model, store, device, batch, global_batch, optimizer, loss, pattern):
-        super().__init__(model, store, device, batch, global_batch, optimizer)
-        from ..ops import kernels as K
-        self.K = K
-        self.loss = loss
-        c, d1, d2 = pattern["conv"], pattern["dense1"], pattern["dense2"]
-        self.c, self.d1, self.d2 = c, d1, d2
+        # read by _size_replicas, which the base constructor calls
         self.f32 = Kb.global_policy().compute_dtype == torch.float32
-        self.compute_dtype = "fp32" if self.f32 else "bf16"
-        H, W = c.input_shape[0], c.input_shape[1]
-        self.H, self.W, self.C = H, W, c.filters
-        Hp, Wp = (H - 2) // 2, (W - 2) // 2
-        self.Kf = Hp * Wp * self.C
-        self.Hd, self.Cls = d1.units, d2.units
-        B, Bp = self.B, _round8(self.B)
-        self.Bp = Bp
-        dev = self.device
-        self.Pt = torch.zeros(self.Kf, Bp, dtype=torch.float32 if self.f32 else torch.bfloat16, device=dev)
-        self.amax = torch.zeros(self.Kf // 32, 4, Bp, dtype=torch.int64, device=dev)  # [P][C/8][B] argmax bytes
-        # Dense(64) pre-activation: two training buffers by step parity + one for eval / predict
-        # (training buffers: hrep replicas each, so the forward's ~85 split-K adders per address spread out)
-        self.hrep = max(1, min(8, int(os.environ.get("TDE_CONVNET_HREP", "4"))))
         # TDE_DETERMINISTIC=1 (debugging): one pre-activation replica per forward workgroup (each address
         # receives exactly one add, into zeros; the consumer sums the replicas in order) and the conv
         # gradients as per-workgroup partials summed in order by an extra launch: bitwise-reproducible
         # training steps at the cost of 2.8 MB of replicas and one launch per step
         self.det = os.environ.get("TDE_DETERMINISTIC", "0") not in ("", "0")
-        P_ = ((H - 2) // 2) * ((W - 2) // 2)
-        if self.det:
-            self.hrep = P_
-        self.cpart = torch.zeros((P_ + 1) * 320, dtype=torch.float32, device=dev) if self.det else None
-        self.n_cpart = P_
-        self.hpre2 = torch.zeros(2, self.hrep, B, self.Hd, dtype=torch.float32, device=dev)
-        self.hpre = torch.zeros(B, self.Hd, dtype=torch.float32, device=dev)
-        self.parity = 0
-        self.probs = torch.zeros(B, self.Cls, dtype=torch.float32, device=dev)
-        self.pre_relu = d1.activation == "relu"
-        self.logits_out = d2.activation is None
-        n = lambda l, w: f"{l.name}/{w}"  # noqa: E731
-        self.names = dict(wc=n(c, "kernel"), bc=n(c, "bias"), w1=n(d1, "kernel"),
-                          b1=n(d1, "bias") if d1.use_bias else None, w2=n(d2, "kernel"), b2=n(d2, "bias"))
+        super().__init__(model, store, device, batch, global_batch, optimizer, pattern)
+        self.loss = loss
+        self.compute_dtype = "fp32" if self.f32 else "bf16"
+        Kf, Bp, dev = self.P * self.C, _round8(self.B), self.device
+        self.Pt = torch.zeros(Kf, Bp, dtype=torch.float32 if self.f32 else torch.bfloat16, device=dev)
+        self.amax = torch.zeros(Kf // 32, 4, Bp, dtype=torch.int64, device=dev)  # [P][C/8][B] argmax bytes
+        self.cpart = torch.zeros((self.P + 1) * 320, dtype=torch.float32, device=dev) if self.det else None
         # bf16: the forward reads the Dense(64) kernel from the row-major bf16 shadow (the one the
         # backward reads and the fused updates rewrite); TDE_CONVNET_W1=col keeps a transposed [64, K]
         # copy for it.  f32: both read the f32 master kernel itself (no shadow exists).
@@ -439,65 +627,28 @@ class ConvNetPlan(ReplicaPlan):
             self.W1row = ok.shadow_views[(self.names["w1"], "row")]
             self.W1col = None if self.w1_rows else ok.shadow_views[(self.names["w1"], "col")]
         self.W1fwd = self.W1row if self.w1_rows else self.W1col
-        # fused step ("local"): conv gradients by step parity (the deferred update of step t is read by
-        # forward t+1 while backward t+1 accumulates the next), their pending flags, and the step count
-        # the deferred update belongs to
-        seg = store.segments
-        sw, sb = seg[self.names["wc"]], seg[self.names["bc"]]
-        self._conv_lo = min(sw.offset, sb.offset)
-        span = max(sw.offset + sw.numel, sb.offset + sb.numel) - self._conv_lo
-        # the ~170 backward workgroups add their conv-gradient partials into crep replicas (workgroup x ->
-        # replica x % crep, summed by the consumers): same-address float atomics from every workgroup cost
-        # ~4 us of the backward (TDE_CONVNET_GREP, 1 = one buffer; the deterministic mode keeps one)
-        self.crep = 1 if self.det else max(1, min(8, int(os.environ.get("TDE_CONVNET_GREP", "8"))))
-        self._conv_span = span
-        # data-parallel step (mode "xgmi", float32 form): the replicas of parity 0 take the conv gradients
-        # and the all-reduce sums them into its push (only when nothing else lies between the two segments)
-        others = [n for n in store.order if n not in (self.names["wc"], self.names["bc"]) and
-                  self._conv_lo <= seg[n].offset < self._conv_lo + span]
-        self._xg_rep = self.f32 and self.crep > 1 and not others
-        self.gconv = torch.zeros(2, self.crep, span, dtype=torch.float32, device=dev)
-        self.pend = torch.zeros(2, dtype=torch.int32, device=dev)
         # device counters of the deferred conv update (the local step's invariants, ``step_invariants``):
         # [0] updates committed (by the next backward's head workgroup or the flush), [1] forwards that
         # applied a pending update on the fly
         self.ucount = torch.zeros(2, dtype=torch.int64, device=dev)
-        # fused step: the head variables as of this step's forward ([b1 | W2 | b2], written by the forward),
-        # read by the backward's trunk workgroups while its head workgroup updates the originals
-        C_ = self.Cls
-        self.hsnap = torch.zeros(64 + 64 * C_ + C_, dtype=torch.float32, device=dev)
-        self._hs_b1 = self.hsnap[:64]
-        self._hs_w2 = self.hsnap[64: 64 + 64 * C_].view(64, C_)
-        self._hs_b2 = self.hsnap[64 + 64 * C_:]
-        self.iter_prev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._fopt = self._bopt = self._flush = None
-        # step mode "xgmi" with the fused exchange (set_push): the backward stores dW1 straight into the
-        # xGMI owners' contribution areas; _pushed marks that the step's launch did so (xg_apply_spec)
-        self._push = None
-        self._pushed = False
+        self._commit_count = self.ucount[0]
+        self._fopt = self._bopt = None
+        self._slots = (None, None)
 
-    # ------------------------------------------------------------------ fused step modes
-    def supports_step_mode(self, mode):
-        if mode == "plain":
-            return True
-        return self._opt_fused() and self.device.type == "cuda" and mode in ("local", "xgmi")
+    def _size_replicas(self, foreign):
+        if self.det:   # one split-K replica per forward workgroup, the conv partials in ``cpart``
+            self.hrep, self.crep = self.P, 1
+        # the all-reduce sums the replicas over the whole span: float32 form, nothing else inside it; the
+        # fused step's ranges name the two segments, so it keeps its replicas either way
+        self._xg_rep = self.f32 and self.crep > 1 and not foreign
 
-    def _gconv(self, q):
-        """Pointer that indexes parity q's conv gradients with the flat-buffer offsets."""
-        return self.gconv[q].data_ptr() - 4 * self._conv_lo
-
-    def _gconv_views(self, q):
+    def _conv_ranges(self):
         seg = self.store.segments
-        sw, sb = seg[self.names["wc"]], seg[self.names["bc"]]
-        lo = self._conv_lo
-        return (self.gconv[q, 0, sw.offset - lo: sw.offset - lo + sw.numel].view(sw.shape),
-                self.gconv[q, 0, sb.offset - lo: sb.offset - lo + sb.numel].view(sb.shape))
+        return [(seg[self.names[k]].offset, seg[self.names[k]].numel) for k in ("wc", "bc")]
 
     def set_step_mode(self, mode):
         super().set_step_mode(mode)
-        if mode != "xgmi":
-            self._push = None
-        if mode != getattr(self, "_mode_set", None):
+        if mode != self._mode_set:
             self.gconv.zero_()   # the replicas change roles between the step modes
             self.pend.zero_()
         self._mode_set = mode
@@ -507,93 +658,45 @@ class ConvNetPlan(ReplicaPlan):
             return
         K, st, opt = self.K, self.store, self.optimizer
         self._slots = m, v = K.opt_slots(st, opt)
-        self._opt_key_set = opt.key()
         if mode != "local":
             return
         seg = st.segments
-        conv = [(seg[self.names["wc"]].offset, seg[self.names["wc"]].numel),
-                (seg[self.names["bc"]].offset, seg[self.names["bc"]].numel)]
         P_ = K._P
         self._fopt, self._bopt, self._flush = [], [], []
         for q in (0, 1):
             # forward of parity q: the deferred update of the previous step (parity 1-q), t = iter_prev
-            f = K.step_opt(opt, st.w, None, m, v, self.iter_prev, self.pend[1 - q])
-            f.g = self._gconv(1 - q)
-            f.grep, f.grep_stride = self.crep, self._conv_span
+            f = self._reads_set(K.step_opt(opt, st.w, None, m, v, self.iter_prev, self.pend[1 - q]), 1 - q)
             f.fly_count = self.ucount[1].data_ptr()
             f.hsrc_w2, f.hsrc_b2 = self._v("w2").data_ptr(), self._v("b2").data_ptr()
             f.hsrc_b1 = self._v("b1").data_ptr() if self.names["b1"] is not None else None
             f.hsnap, f.hC = self.hsnap.data_ptr(), self.Cls
             self._fopt.append(f)
-            commit = K.flat_apply_spec(opt, st.w, None, m, v, self.iterations, self.pend[1 - q], conv)
-            commit.g = self._gconv(1 - q)
-            commit.grep, commit.grep_stride = self.crep, self._conv_span
-            commit.count = self.ucount[0].data_ptr()
             b1 = self.names["b1"]
             self._bopt.append(K.BwdOpt(
                 K.opt_hyper(opt), P_(st.w), P_(m), P_(v),
                 seg[self.names["w1"]].offset, seg[self.names["w2"]].offset, seg[self.names["b2"]].offset,
                 seg[b1].offset if b1 is not None else -1, P_(self.W1col),
                 self.W1col.stride(0) if self.W1col is not None else 0, P_(self.iterations), P_(self.iter_prev),
-                commit, self.pend[q].data_ptr(), self.crep, self._conv_span))
-            fl = K.flat_apply_spec(opt, st.w, None, m, v, self.iterations, self.pend[q], conv)
-            fl.g = self._gconv(q)
-            fl.grep, fl.grep_stride = self.crep, self._conv_span
-            fl.count = self.ucount[0].data_ptr()
-            self._flush.append(fl)
+                self._conv_apply(1 - q, m, v), self.pend[q].data_ptr(), self.crep, self._conv_span))
+            self._flush.append(self._conv_apply(q, m, v))
 
     def push_range(self):
-        """Bucket range the backward can push into the xGMI owners itself (the Dense(64) kernel's dW1:
-        99.7 % of the gradient bytes), or None when this plan form cannot."""
-        if not self.f32:
-            return None
-        seg = self.store.segments[self.names["w1"]]
-        return seg.offset, seg.offset + seg.numel
-
-    def set_push(self, spec):
-        """Fused data-parallel exchange (step mode "xgmi"): ``spec`` is the communicator's ``XgPush`` for
-        this replica (None: dW1 to the local bucket, the all-reduce pushes it)."""
-        if spec is not None and (self.step_mode != "xgmi" or self.push_range() is None):
-            raise ValueError("the fused exchange needs step mode 'xgmi' and the float32 plan")
-        self._push = spec
-
-    def refresh(self):
-        # the kernel argument structs carry lr / hyper-parameters by value
-        if self.step_mode != "plain" and self._opt_key_set != self.optimizer.key():
-            self.set_step_mode(self.step_mode)
+        return super().push_range() if self.f32 else None   # the bf16 backward cannot push
 
     def xg_apply_spec(self):
-        """``XgApply`` for the communicator's fused all-reduce (step mode "xgmi")."""
-        st, opt = self.store, self.optimizer
+        if self.f32:   # no shadow: the all-reduce updates the f32 master weights only
+            return super().xg_apply_spec()
+        st, K = self.store, self.K
         m, v = self._slots
         seg = st.segments[self.names["w1"]]
-        K = self.K
-        if self.f32:   # no shadow: the all-reduce updates the f32 master weights only
-            # the step's backward pushed dW1 itself (a replica without data this step pushed nothing)
-            lo, hi = self.push_range() if (self._push is not None and self._pushed) else (0, 0)
-            self._pushed = False
-            spec = K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), None, 0, 0, None,
-                             0, 0, lo, hi)
-            if self._xg_rep:   # the conv gradients wait in the replicas of parity 0
-                spec.rep, spec.nrep = self.gconv[0].data_ptr(), self.crep
-                spec.rep_lo, spec.rep_hi = self._conv_lo, self._conv_lo + self._conv_span
-                spec.rep_stride = self._conv_span
-            return spec
-        return K.XgApply(K.opt_hyper(opt), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations), K._P(self.W1row),
-                         seg.offset, seg.offset + seg.numel, K._P(self.W1col), self.Hd,
+        return K.XgApply(K.opt_hyper(self.optimizer), K._P(st.w), K._P(m), K._P(v), K._P(self.iterations),
+                         K._P(self.W1row), seg.offset, seg.offset + seg.numel, K._P(self.W1col), self.Hd,
                          self.W1col.stride(0) if self.W1col is not None else 0)
 
-    def finish(self):
-        if self.step_mode == "local":
-            # only the last step's conv update can be pending (each backward commits the previous one)
-            self.K.flat_apply(self._flush[1 - self.parity])
-
     def step_invariants(self):
-        """The deferred conv update's state between executions (step mode "local"; synchronises): every
-        step's update committed exactly once, nothing pending, every gradient replica consumed."""
-        torch.cuda.synchronize(self.device)
-        return dict(commits=int(self.ucount[0]), applied_on_the_fly=int(self.ucount[1]),
-                    pending=[int(v) for v in self.pend.cpu()], gconv_abs_max=float(self.gconv.abs().max()))
+        """The base's, and every step's update committed exactly once."""
+        iv = super().step_invariants()
+        return dict(commits=int(self.ucount[0]), applied_on_the_fly=int(self.ucount[1]), **iv)
 
     def trace_tensors(self):
         """Per-step state recorded by ``Program.enable_trace`` (diagnostics)."""
@@ -621,18 +724,7 @@ class ConvNetPlan(ReplicaPlan):
     def on_weights_loaded(self):
         if not self.f32:
             (self.opt or self._shadow_only).refresh_shadows()
-        # loaded weights replace whatever update was outstanding
-        self.pend.zero_()
-        self.gconv.zero_()
-        self.store.g.zero_()
-
-    def _v(self, key):
-        nm = self.names[key]
-        return None if nm is None else self.store.view(nm)
-
-    def _g(self, key):
-        nm = self.names[key]
-        return None if nm is None else self.store.grad(nm)
+        super().on_weights_loaded()
 
     def _forward(self, x, B, hpre, with_pt, opt=None, train=False, hrep=1):
         # launch 1: conv+bias+ReLU+pool fused with the Dense(Hd) matmul (split-K atomics into hpre,
@@ -643,59 +735,31 @@ class ConvNetPlan(ReplicaPlan):
                            off_wc=seg[self.names["wc"]].offset, off_bc=seg[self.names["bc"]].offset,
                            inc_iter=self.iterations if train else None, hrep=hrep)
 
+    def _infer_forward(self, x, B):
+        self._forward(x, B, self.hpre, False)
+
     def train_step(self, x, y, B=None):
         K = self.K
         B = self.B if B is None else B
         q = self.parity
         local = self.step_mode == "local"
         self._forward(x, B, self.hpre2[q], True, self._fopt[q] if local else None, train=True, hrep=self.hrep)
-        # launch 2: head + trunk backward (fused step: the updates too)
-        xg = self.step_mode == "xgmi"
-        rep = xg and self._xg_rep
-        if local or rep:
-            dwc, dbc = self._gconv_views(q if local else 0)
-        else:
-            dwc, dbc = self._g("wc"), self._g("bc")
-        push = self._push if xg else None
-        if local:   # the head variables as of the forward (the backward's head workgroup updates the originals)
-            b1, w2, b2 = (self._hs_b1 if self.names["b1"] is not None else None), self._hs_w2, self._hs_b2
-        else:
-            b1, w2, b2 = self._v("b1"), self._v("w2"), self._v("b2")
+        # launch 2: head + trunk backward (fused step: the updates too, and its descriptor carries crep)
+        dwc, dbc, sets = self._conv_grads(q)
+        push = self._push if self.step_mode == "xgmi" else None
+        b1, w2, b2 = self._head_vars()
         K.convnet_bwd(x, self.amax, self.hpre2[q], self.hpre2[1 - q], b1, w2, b2, y,
                       scale=self.scale, pre_relu=self.pre_relu, metrics=self.metrics, W1row=self.W1row, Pt=self.Pt,
                       dW1=self._g("w1"), dwc=dwc, dbc=dbc, dW2=self._g("w2"), db2=self._g("b2"), db1=self._g("b1"),
                       B=B, opt=self._bopt[q] if local else None, cpart=self.cpart, push=push,
-                      crep=self.crep if rep else 1, crep_stride=self._conv_span)
+                      crep=self.crep if sets and not local else 1, crep_stride=self._conv_span)
         self._pushed = push is not None
         if self.det:
-            K.convnet_cgrad_reduce(self.cpart, self.n_cpart, dwc, dbc)
+            K.convnet_cgrad_reduce(self.cpart, self.P, dwc, dbc)
         self.parity = 1 - q
 
-    def apply(self):
-        # step mode "plain": multi-tensor optimizer (+ grad zeroing + bf16 shadow refresh)
-        self.opt.apply()
 
-    def eval_step(self, x, y, B=None):
-        B = self.B if B is None else B
-        self._forward(x, B, self.hpre, False)
-        self.K.head_xent(self.hpre, self._v("w2"), self._v("b2"), y, B=B, scale=self.scale, pre_bias=self._v("b1"),
-                         pre_relu=self.pre_relu, compute_grad=False, metrics=self.metrics, zero_hin=True)
-
-    def predict(self, x, B=None):
-        B = self.B if B is None else B
-        self._forward(x, B, self.hpre, False)
-        self.K.head_xent(self.hpre, self._v("w2"), self._v("b2"), self._dummy_labels(B), B=B, scale=1.0,
-                         pre_bias=self._v("b1"), pre_relu=self.pre_relu, compute_grad=False, probs=self.probs,
-                         probs_are_logits=self.logits_out, zero_hin=True)
-        return self.probs[:B]
-
-    def _dummy_labels(self, B):
-        if not hasattr(self, "_zl") or self._zl.shape[0] < B:
-            self._zl = torch.zeros(max(B, self.B), dtype=torch.int32, device=self.device)
-        return self._zl
-
-
-class ConvNetGenPlan(ReplicaPlan):
+class ConvNetGenPlan(SmallCnnPlan):
     """The DWK/TF2M small CNN at the user's own widths — Conv2D(F in 16/32/48/64) · MaxPool(2) · Flatten ·
     Dense(U in 32/64/96/128) · Dense(<= 16) (distributed_with_keras.py:33-43 and tf2_mnist_distributed.py:66-72
     with other filter / unit counts) — as two fused float32 HIP launches per step (csrc/kernels/convnet_gen.hip):
@@ -714,79 +778,33 @@ class ConvNetGenPlan(ReplicaPlan):
     reference's own Conv2D(32)/Dense(64) keeps the hand-tuned ``ConvNetPlan``."""
     kind = "fused_convnet_generic"
 
+    hyper_by_value = ("local",)
+
     def __init__(self, model, store, device, batch, global_batch, optimizer, loss, pattern):
-        super().__init__(model, store, device, batch, global_batch, optimizer)
         from ..ops import kernels as K
-        self.K = K
-        c, d1, d2 = pattern["conv"], pattern["dense1"], pattern["dense2"]
+        c, d1 = pattern["conv"], pattern["dense1"]
         if not K.cgen_supported(c.filters, d1.units):
             raise NotImplementedError(f"convnet_gen: Conv2D({c.filters}) + Dense({d1.units}) not instantiated")
         if os.environ.get("TDE_DETERMINISTIC", "0") not in ("", "0"):
             import warnings
             warnings.warn("TDE_DETERMINISTIC: the generic-width fused CNN step adds its split-K and conv-gradient "
                           "partials with float atomics; its steps are not bitwise reproducible")
-        self.H, self.W, self.C = c.input_shape[0], c.input_shape[1], c.filters
-        self.P = ((self.H - 2) // 2) * ((self.W - 2) // 2)
-        self.Hd, self.Cls = d1.units, d2.units
-        B, Bp, dev = self.B, _round8(self.B), self.device
+        super().__init__(model, store, device, batch, global_batch, optimizer, pattern)
+        Bp, dev = _round8(self.B), self.device
         self.Pt = torch.zeros(self.P * self.C, Bp, dtype=torch.float32, device=dev)
         self.amax = torch.zeros(self.P, self.C // 8, Bp, dtype=torch.int64, device=dev)
-        # split-K targets of the forward's ~P adders per address, summed by the consumers (TDE_CONVNET_HREP)
-        self.hrep = max(1, min(8, int(os.environ.get("TDE_CONVNET_HREP", "4"))))
-        self.hpre2 = torch.zeros(2, self.hrep, B, self.Hd, dtype=torch.float32, device=dev)
-        self.hpre = torch.zeros(B, self.Hd, dtype=torch.float32, device=dev)
-        self.probs = torch.zeros(B, self.Cls, dtype=torch.float32, device=dev)
-        self.pre_relu = d1.activation == "relu"
-        self.logits_out = d2.activation is None
-        n = lambda l, w: f"{l.name}/{w}"  # noqa: E731
-        self.names = dict(wc=n(c, "kernel"), bc=n(c, "bias"), w1=n(d1, "kernel"),
-                          b1=n(d1, "bias") if d1.use_bias else None, w2=n(d2, "kernel"), b2=n(d2, "bias"))
         self.W1 = store.view(self.names["w1"])
         self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
-        self.parity = 0
-        self._copt = self._fly = self._hopt = self._commit = self._flush = None
-        self._push, self._pushed = None, False
-        # conv gradients: the ~170 backward workgroups add theirs into crep replicas of the conv segments
-        # (workgroup x -> replica x % crep; same-address float atomics from every workgroup serialise at the
-        # memory side), summed by the consumer: in the fused step the next forward (the update applied on the
-        # fly) and the next backward's head workgroup (committed), one set per step parity; under data
-        # parallelism the xGMI all-reduce (set 0).  TDE_CONVNET_GREP; plain steps add into the gradient bucket.
-        seg = store.segments
-        sw, sb = seg[self.names["wc"]], seg[self.names["bc"]]
-        self._conv_lo = min(sw.offset, sb.offset)
-        self._conv_span = max(sw.offset + sw.numel, sb.offset + sb.numel) - self._conv_lo
-        others = [n for n in store.order if n not in (self.names["wc"], self.names["bc"]) and
-                  self._conv_lo <= seg[n].offset < self._conv_lo + self._conv_span]
-        self.crep = 1 if others else max(1, min(8, int(os.environ.get("TDE_CONVNET_GREP", "8"))))
-        self.gconv = torch.zeros(2, self.crep, self._conv_span, dtype=torch.float32, device=dev)
-        # fused step: the deferred conv update's flags by parity, Adam's t of the pending update, and the head
-        # variables as of the forward ([b1 | W2 | b2]: the backward's trunk reads them while its head workgroup
-        # updates the originals)
-        self.pend = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.iter_prev = torch.zeros(1, dtype=torch.int64, device=dev)
-        C_, H_ = self.Cls, self.Hd
-        self.hsnap = torch.zeros(H_ + H_ * C_ + C_, dtype=torch.float32, device=dev)
-        self._hs_b1 = self.hsnap[:H_]
-        self._hs_w2 = self.hsnap[H_: H_ + H_ * C_].view(H_, C_)
-        self._hs_b2 = self.hsnap[H_ + H_ * C_:]
+        self._copt = self._fly = self._hopt = self._commit = None
 
-    def supports_step_mode(self, mode):
-        if mode == "plain":
-            return True
-        ok = self._opt_fused() and self.device.type == "cuda"
-        return ok and mode in ("xgmi", "local")
-
-    def _gset(self, q, name):
-        """Replica 0 of conv variable ``name``'s gradient in parity set q."""
-        sg = self.store.segments[self.names[name]]
-        lo = self._conv_lo
-        return self.gconv[q, 0, sg.offset - lo: sg.offset - lo + sg.numel]
+    def _size_replicas(self, foreign):
+        if foreign:   # every consumer here walks one range over the whole span
+            self.crep = 1
+        self._xg_rep = self.crep > 1
 
     def set_step_mode(self, mode):
         super().set_step_mode(mode)
         self._copt = self._fly = self._hopt = self._commit = self._flush = None
-        if mode != "xgmi":
-            self._push = None
         self.gconv.zero_()
         self.pend.zero_()
         if mode != "local":
@@ -797,7 +815,6 @@ class ConvNetGenPlan(ReplicaPlan):
         seg = st.segments
         at = lambda t, name: None if t is None or name is None else t.data_ptr() + 4 * seg[self.names[name]].offset  # noqa: E731
         self._copt = K.CgenOpt(h, at(st.w, "w1"), at(m, "w1"), at(v, "w1"), self.iterations.data_ptr())
-        conv = [(self._conv_lo, self._conv_span)]
         self._fly, self._hopt, self._commit, self._flush = [], [], [], []
         for q in (0, 1):
             # forward of parity q: the update of the previous step (set 1-q) on the fly, the head snapshot
@@ -811,68 +828,11 @@ class ConvNetGenPlan(ReplicaPlan):
                 h, st.w.data_ptr(), K._P(m), K._P(v), seg[self.names["w2"]].offset, seg[self.names["b2"]].offset,
                 seg[b1].offset if b1 is not None else -1, self.iterations.data_ptr(), self.pend[q].data_ptr(),
                 self.iter_prev.data_ptr()))
-            for lst, qq in ((self._commit, 1 - q), (self._flush, q)):
-                f = K.flat_apply_spec(o, st.w, None, m, v, self.iterations, self.pend[qq], conv)
-                f.g = self.gconv[qq].data_ptr() - 4 * self._conv_lo   # indexed with the flat offsets
-                f.grep, f.grep_stride = self.crep, self._conv_span
-                lst.append(f)
-        self._opt_key_set = o.key()
+            self._commit.append(self._conv_apply(1 - q, m, v))
+            self._flush.append(self._conv_apply(q, m, v))
 
-    def finish(self):
-        if self.step_mode == "local":
-            # only the last step's conv update can be pending (each backward commits the previous one)
-            self.K.flat_apply(self._flush[1 - self.parity])
-
-    def refresh(self):
-        # the launch descriptors carry lr / hyper-parameters by value
-        if self.step_mode == "local" and self._opt_key_set != self.optimizer.key():
-            self.set_step_mode("local")
-
-    def push_range(self):
-        """Bucket range the backward can push into the xGMI owners itself: the Dense(U) kernel's gradient."""
-        seg = self.store.segments[self.names["w1"]]
-        return seg.offset, seg.offset + seg.numel
-
-    def set_push(self, spec):
-        """Fused data-parallel exchange (step mode "xgmi"): ``spec`` is the communicator's ``XgPush``."""
-        if spec is not None and self.step_mode != "xgmi":
-            raise ValueError("the fused exchange needs step mode 'xgmi'")
-        self._push = spec
-
-    def xg_apply_spec(self):
-        spec = f32_xg_apply_spec(self)
-        if self.crep > 1:   # the conv gradients wait in the replicas: the all-reduce sums (and zeroes) them
-            spec.rep, spec.nrep = self.gconv[0].data_ptr(), self.crep
-            spec.rep_lo, spec.rep_hi = self._conv_lo, self._conv_lo + self._conv_span
-            spec.rep_stride = self._conv_span
-        return spec
-
-    def _conv_grads(self, q):
-        """(dwc, dbc, crep, stride) the backward of parity q adds the conv gradients into."""
-        if self.step_mode == "plain" or (self.step_mode == "xgmi" and self.crep == 1):
-            return self._g("wc"), self._g("bc"), 1, 0
-        qs = q if self.step_mode == "local" else 0
-        return self._gset(qs, "wc"), self._gset(qs, "bc"), self.crep, self._conv_span
-
-    def step_invariants(self):
-        """The deferred conv update's state between executions (step mode "local"; synchronises): nothing
-        pending, every gradient replica consumed."""
-        torch.cuda.synchronize(self.device)
-        return dict(pending=[int(v) for v in self.pend.cpu()], gconv_abs_max=float(self.gconv.abs().max()))
-
-    def _v(self, key):
-        nm = self.names[key]
-        return None if nm is None else self.store.view(nm)
-
-    def _g(self, key):
-        nm = self.names[key]
-        return None if nm is None else self.store.grad(nm)
-
-    def on_weights_loaded(self):
-        # loaded weights replace whatever gradients were outstanding
-        self.store.g.zero_()
-        self.gconv.zero_()
-        self.pend.zero_()
+    def _infer_forward(self, x, B):
+        self.K.cgen_fwd(x, self._v("wc"), self._v("bc"), self.W1, self.hpre, self.Pt, self.amax, B=B)
 
     def train_step(self, x, y, B=None):
         K = self.K
@@ -882,42 +842,18 @@ class ConvNetGenPlan(ReplicaPlan):
         # the fused step's Adam t is read by every backward workgroup: the forward advances the counter
         K.cgen_fwd(x, self._v("wc"), self._v("bc"), self.W1, self.hpre2[q], self.Pt, self.amax, B=B,
                    inc_iter=self.iterations if local else None, fly=self._fly[q] if local else None)
-        dwc, dbc, crep, cstride = self._conv_grads(q)
+        dwc, dbc, sets = self._conv_grads(q)
         push = self._push if self.step_mode == "xgmi" else None
-        if local:   # the head as of this step's forward (the head workgroup updates the originals)
-            b1, w2, b2 = (self._hs_b1 if self.names["b1"] is not None else None), self._hs_w2, self._hs_b2
-        else:
-            b1, w2, b2 = self._v("b1"), self._v("w2"), self._v("b2")
+        b1, w2, b2 = self._head_vars()
         K.cgen_bwd(x, self.amax, self.hpre2[q], self.hpre2[1 - q], b1, w2, b2, y,
                    scale=self.scale, pre_relu=self.pre_relu, metrics=self.metrics, W1=self.W1, Pt=self.Pt,
-                   dW1=None if local else self._g("w1"), dwc=dwc.view(self._v("wc").shape), dbc=dbc, dW2=self._g("w2"),
+                   dW1=None if local else self._g("w1"), dwc=dwc, dbc=dbc, dW2=self._g("w2"),
                    db2=self._g("b2"), db1=self._g("b1"), B=B, iterations=None if local else self.iterations,
-                   opt=self._copt if local else None, crep=crep, crep_stride=cstride,
+                   opt=self._copt if local else None, crep=self.crep if sets else 1,
+                   crep_stride=self._conv_span if sets else 0,
                    hopt=self._hopt[q] if local else None, fcommit=self._commit[q] if local else None, push=push)
         self._pushed = push is not None
         self.parity = 1 - q
-
-    def apply(self):
-        self.opt.apply()
-
-    def _forward(self, x, B):
-        self.K.cgen_fwd(x, self._v("wc"), self._v("bc"), self.W1, self.hpre, self.Pt, self.amax, B=B)
-
-    def eval_step(self, x, y, B=None):
-        B = self.B if B is None else B
-        self._forward(x, B)
-        self.K.head_xent(self.hpre, self._v("w2"), self._v("b2"), y, B=B, scale=self.scale, pre_bias=self._v("b1"),
-                         pre_relu=self.pre_relu, compute_grad=False, metrics=self.metrics, zero_hin=True)
-
-    def predict(self, x, B=None):
-        B = self.B if B is None else B
-        self._forward(x, B)
-        if not hasattr(self, "_zl"):
-            self._zl = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.K.head_xent(self.hpre, self._v("w2"), self._v("b2"), self._zl, B=B, scale=1.0,
-                         pre_bias=self._v("b1"), pre_relu=self.pre_relu, compute_grad=False, probs=self.probs,
-                         probs_are_logits=self.logits_out, zero_hin=True)
-        return self.probs[:B]
 
 
 # ---------------------------------------------------------------------------------------

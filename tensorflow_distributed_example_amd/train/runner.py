@@ -204,7 +204,7 @@ class Program:
         self.exchange = "post_backward"
         if os.environ.get("TDE_XGMI_PUSH", "1") == "0" or not hasattr(self.comm, "push_spec"):
             return
-        if not all(hasattr(p, "push_range") and p.push_range() is not None for p in self.plans):
+        if not all(p.push_range() is not None for p in self.plans):
             return
         for i, p in enumerate(self.plans):
             lo, _ = p.push_range()

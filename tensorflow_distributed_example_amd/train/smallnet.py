@@ -274,10 +274,6 @@ class SmallNetPlan(ReplicaPlan):
             return self._opt_fused() and self.device.type == "cuda"
         return mode == "plain" or (mode == "local" and self.optimizer is not None and self.device.type == "cuda")
 
-    def xg_apply_spec(self):
-        from .program import f32_xg_apply_spec
-        return f32_xg_apply_spec(self)
-
     def set_iterations(self, step):
         super().set_iterations(step)
         if self.step_word is not None:

@@ -293,6 +293,43 @@ def test_bncnn_fused_reduce_optimizer_matches_separate_launch(kind):
         assert torch.equal(sp[k], sl[k]), k
 
 
+def test_bncnn_local_graph_picks_up_learning_rate_change(monkeypatch):
+    """A hyper-parameter change between two hipGraph executions, step mode "local" against "plain"
+    (TDE_FUSED_STEP=0): momentum SGD, batch 16, dropout on, two executions of two steps over the same data,
+    the learning rate halved on both models in between.  The reduce launch's descriptor carries the rate by
+    value, so the change has to go through ``refresh()``, the descriptor rebuild and the Program's recapture;
+    a missed refresh applies the old rate for two steps.  After each execution weights and slots are bitwise
+    equal, the bound of ``test_bncnn_fused_reduce_optimizer_matches_separate_launch``; the step counter ends
+    at 4."""
+    import tensorflow_distributed_example_amd as tde
+    progs = []
+    for mode in ("local", "plain"):
+        if mode == "plain":
+            monkeypatch.setenv("TDE_FUSED_STEP", "0")
+        tde.backend.set_random_seed(11)
+        m = _model_b(tde, rate=0.3, opt=tde.optimizers.SGD(0.05, momentum=0.9))
+        m.steps_per_execution = 2
+        prog = m._program("train", 16)
+        assert prog.use_graph and prog.plan_kind == "fused_bncnn" and prog.plans[0].step_mode == mode
+        progs.append((m, prog))
+    (ml, pl), (mp, pp) = progs
+    assert torch.equal(ml._store.w, mp._store.w)
+    data = [_data(16, 40 + s) for s in range(2)]
+    xs, ys = torch.stack([d[0] for d in data]), torch.stack([d[1] for d in data])
+    for e in range(2):
+        for prog in (pl, pp):
+            prog.stage([(xs, ys)])
+            prog.run()
+            prog.sync()
+        sl, sp = ml._store, mp._store
+        print(f"execution {e}: local vs plain max |dw| {float((sl.w - sp.w).abs().max()):.3e}")
+        assert torch.equal(sl.w, sp.w), (e, float((sl.w - sp.w).abs().max()))
+        for k in sp.slots:
+            assert torch.equal(sl.slots[k], sp.slots[k]), (e, k)
+        ml.optimizer.learning_rate = mp.optimizer.learning_rate = 0.025
+    assert int(pl.plans[0].iterations) == int(pp.plans[0].iterations) == 4
+
+
 @pytest.mark.parametrize("B", [128, 50])
 def test_bncnn_dropout_matches_float64_with_the_plan_mask(B):
     """Dropout(0.5) of Model B as the reference trains it (mnist_keras_distributed.py:106): the fused head's

@@ -211,6 +211,45 @@ def test_generic_plan_graph_trajectory_matches_float64(filters, units, mode, kin
             assert float(st.g.abs().max()) == 0.0
 
 
+def test_generic_plan_local_graph_picks_up_learning_rate_change(monkeypatch):
+    """A hyper-parameter change between two hipGraph executions at Conv2D(16)/Dense(32), step mode "local"
+    against "plain" (TDE_FUSED_STEP=0): momentum SGD, batch 16, two executions of two steps over the same data,
+    the learning rate halved on both models in between.  The local plan's descriptors carry the rate by value,
+    so the change has to go through ``refresh()``, the descriptor rebuild and the Program's recapture; a missed
+    refresh applies the old rate for two steps (~1e-3).  After each execution every variable agrees within the
+    momentum bounds of ``test_generic_plan_graph_trajectory_matches_float64`` (biases 5e-4, the conv kernel
+    5e-5, the Dense kernels 1e-5); the step counter ends at 4 with nothing pending and every replica consumed."""
+    import tensorflow_distributed_example_amd as tde
+    O = tde.optimizers
+    ml = _model(tde, 16, 32, O.SGD(0.02, momentum=0.9), 2)
+    w0 = ml._store.w.clone()
+    pl = ml._program("train", 16)
+    monkeypatch.setenv("TDE_FUSED_STEP", "0")
+    mp = _model(tde, 16, 32, O.SGD(0.02, momentum=0.9), 2)
+    mp._store.w.copy_(w0)
+    pp = mp._program("train", 16)
+    a, b = pl.plans[0], pp.plans[0]
+    assert pl.use_graph and pp.use_graph and a.kind == b.kind == "fused_convnet_generic"
+    assert a.step_mode == "local" and b.step_mode == "plain"
+    data = [_qdata(16, 500 + s) for s in range(2)]
+    xs, ys = torch.stack([d[0] for d in data]), torch.stack([d[1] for d in data])
+    for e in range(2):
+        for prog in (pl, pp):
+            prog.stage([(xs, ys)])
+            prog.run()
+            prog.sync()
+        for n, n_plain in zip(ml._store.names(trainable=True), mp._store.names(trainable=True)):
+            bias, conv = n.endswith("/bias"), n == f"{ml.layers[0].name}/kernel"
+            tol = 5e-4 if bias else (5e-5 if conv else 1e-5)
+            r = _rel(ml._store.view(n), mp._store.view(n_plain))
+            print(f"execution {e} {n}: local vs plain {r:.3e} (bound {tol:g})")
+            assert r < tol, (e, n, r)
+        ml.optimizer.learning_rate = mp.optimizer.learning_rate = 0.01
+    assert int(a.iterations) == int(b.iterations) == 4
+    iv = a.step_invariants()
+    assert iv["pending"] == [0, 0] and iv["gconv_abs_max"] == 0.0, iv
+
+
 def test_generic_plan_fit_evaluate_predict():
     """Keras surface on the generic plan: fit() learns a separable synthetic task, evaluate() and predict()
     agree with the torch reference executor at the same weights."""

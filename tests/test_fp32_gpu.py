@@ -399,3 +399,40 @@ def test_fp32_fused_graph_trajectory_deterministic_mode_tight(monkeypatch):
         iv = plan.step_invariants()
         assert iv["commits"] == 4 * (e + 1) and iv["applied_on_the_fly"] == 3 * (e + 1), iv
         assert iv["pending"] == [0, 0] and iv["gconv_abs_max"] == 0.0, iv
+
+
+def test_fp32_local_graph_picks_up_learning_rate_change(monkeypatch):
+    """A hyper-parameter change between two hipGraph executions, step mode "local" against "plain"
+    (TDE_FUSED_STEP=0): momentum SGD, batch 16, two executions of two steps over the same data, the learning
+    rate halved on both models in between.  The local plan's descriptors carry the rate by value, so the
+    change has to go through ``refresh()``, the descriptor rebuild and the Program's recapture; a missed
+    refresh applies the old rate for two steps (~1e-3 of |w|).  After each execution every variable agrees
+    to 1e-6 relative, the bound of ``test_fp32_fused_local_step_matches_float64_sgd[momentum]``; the step
+    counter ends at 4 with nothing pending and every gradient replica consumed."""
+    import tensorflow_distributed_example_amd as tde
+    O = tde.optimizers
+    ml = _model(tde, O.SGD(0.05, momentum=0.9), spe=2)
+    w0 = ml._store.w.clone()
+    pl = ml._program("train", 16)
+    monkeypatch.setenv("TDE_FUSED_STEP", "0")
+    mp = _model(tde, O.SGD(0.05, momentum=0.9), spe=2)
+    mp._store.w.copy_(w0)
+    pp = mp._program("train", 16)
+    a, b = pl.plans[0], pp.plans[0]
+    assert pl.use_graph and pp.use_graph and a.kind == b.kind == "fused_convnet"
+    assert a.step_mode == "local" and b.step_mode == "plain"
+    data = [_qdata(16, 400 + s) for s in range(2)]
+    xs, ys = torch.stack([d[0] for d in data]), torch.stack([d[1] for d in data])
+    for e in range(2):
+        for prog in (pl, pp):
+            prog.stage([(xs, ys)])
+            prog.run()
+            prog.sync()
+        for n, n_plain in zip(ml._store.names(trainable=True), mp._store.names(trainable=True)):
+            r = _rel(ml._store.view(n), mp._store.view(n_plain))
+            print(f"execution {e} {n}: local vs plain {r:.3e}")
+            assert r < 1e-6, (e, n, r)
+        ml.optimizer.learning_rate = mp.optimizer.learning_rate = 0.025
+    assert int(a.iterations) == int(b.iterations) == 4
+    iv = a.step_invariants()
+    assert iv["pending"] == [0, 0] and iv["gconv_abs_max"] == 0.0, iv

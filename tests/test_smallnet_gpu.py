@@ -124,6 +124,44 @@ def test_smallnet_local_step_matches_plain(opt):
     assert a.iterations.item() == b.iterations.item() == 3
 
 
+def test_smallnet_local_graph_picks_up_learning_rate_change(monkeypatch):
+    """A hyper-parameter change between two hipGraph executions on LeNet-5, step mode "local" against "plain"
+    (TDE_FUSED_STEP=0): momentum SGD, batch 16, two executions of two steps over the same data, the learning
+    rate halved on both models in between.  The captured launches hold the rate as a kernel argument, so the
+    change has to reach them through the Program's recapture; a missed one applies the old rate for two
+    steps.  After each execution every variable's accumulated update agrees to 1e-5 relative, the bound of
+    ``test_smallnet_local_step_matches_plain``; the step counter ends at 4."""
+    import tensorflow_distributed_example_amd as tde
+    progs = []
+    for mode in ("local", "plain"):
+        if mode == "plain":
+            monkeypatch.setenv("TDE_FUSED_STEP", "0")
+        tde.backend.set_random_seed(3)
+        m = _build(tde, "lenet5", tde.optimizers.SGD(0.05, momentum=0.9))
+        m.steps_per_execution = 2
+        prog = m._program("train", 16)
+        assert prog.use_graph and prog.plan_kind == "fused_smallnet" and prog.plans[0].step_mode == mode
+        progs.append((m, prog))
+    (ml, pl), (mp, pp) = progs
+    w0 = ml._store.w.clone()
+    assert torch.equal(w0, mp._store.w)
+    x, y = _data(ml, 32, 20)
+    xs, ys = x.view(2, 16, *x.shape[1:]), y.view(2, 16)
+    for e in range(2):
+        for prog in (pl, pp):
+            prog.stage([(xs, ys)])
+            prog.run()
+            prog.sync()
+        for n, n_plain in zip(ml._store.names(trainable=True), mp._store.names(trainable=True)):
+            sg = ml._store.segments[n]
+            w = w0[sg.offset: sg.offset + sg.numel].view(sg.shape)
+            r = _rel(ml._store.view(n) - w, mp._store.view(n_plain) - w)    # the accumulated updates
+            print(f"execution {e} {n}: local vs plain {r:.3e}")
+            assert r < 1e-5, (e, n, r)
+        ml.optimizer.learning_rate = mp.optimizer.learning_rate = 0.025
+    assert int(pl.plans[0].iterations) == int(pp.plans[0].iterations) == 4
+
+
 def test_smallnet_fit_lenet5():
     """fit() on LeNet-5 picks the fused small-net plan (hipGraph executions, the in-step optimizer) and
     learns a separable synthetic task."""
