@@ -32,6 +32,7 @@
 #include "tde_common.h"
 #include "tde_optim.h"
 #include "tde_philox.h"
+#include "tde_sched.h"
 
 namespace tde {
 
@@ -1081,24 +1082,44 @@ struct SnWgradArgs {
   float* metrics;
   OptHyper h;
 };
+// ... of smallnet_wgrad_sched_kernel: the schedule appended.  A struct of its own, because the same two fields
+// at the end of SnWgradArgs let the compiler widen the RMSprop variant's last kernarg load (44 -> 46 SGPRs,
+// profiles/lr_schedule/NOTES.md); this way the two other kernels keep their program to the instruction.
+struct SnWgradSchedArgs : SnWgradArgs {
+  LrSched sched;   // the learning-rate schedule (replaces h.lr)
+  float* lr_out;   // nullable: block 0 stores the step's rate here
+};
 
 // EXT = false: gradient store, or the in-step update of kinds 0..3.  EXT = true: the in-step update of the
 // RMSprop kinds (rms is `m`, the momentum accumulator `v`), launched for kinds 4 / 5 with apply = 1 only, so
-// the other kinds keep the program they had.
-template <bool EXT>
-__device__ __forceinline__ void sn_commit(const SnWgradArgs& a, int e, float grad, float lr_t) {
-  if (!EXT && !a.apply) {
-    a.g[e] = grad;
-    return;
+// the other kinds keep the program they had.  SCHED (with EXT): the in-step update of any kind 0..5 under a
+// learning-rate schedule, apply = 1 only; `h` is the kernel's copy of a.h with the step's rate in it.  Which
+// slots a kind has is asked of opt_uses_m / opt_uses_v there, opt_has_m<true> being true for every kind.
+template <bool EXT, bool SCHED, class Args>
+__device__ __forceinline__ void sn_commit(const Args& a, const OptHyper& h, int e, float grad, float lr_t) {
+  if constexpr (SCHED) {
+    float ms = opt_uses_m(h.kind) ? a.m[e] : 0.f;
+    float vs = opt_uses_v(h.kind) ? a.v[e] : 0.f;
+    a.w[e] = opt_step<true>(h, lr_t, a.w[e], grad, ms, vs);
+    if (opt_uses_m(h.kind)) a.m[e] = ms;
+    if (opt_uses_v(h.kind)) a.v[e] = vs;
+  } else {
+    if (!EXT && !a.apply) {
+      a.g[e] = grad;
+      return;
+    }
+    opt_step_at<EXT>(a.h, lr_t, a.w, a.m, a.v, e, grad);
   }
-  opt_step_at<EXT>(a.h, lr_t, a.w, a.m, a.v, e, grad);
 }
 
-template <bool EXT>
-__device__ __forceinline__ void sn_wgrad(const SnWgradArgs a) {
+template <bool EXT, bool SCHED = false, class Args>
+__device__ __forceinline__ void sn_wgrad(const Args a) {
   __shared__ float red[8][33];
   const int blk = blockIdx.x, tid = threadIdx.x;
-  const float lr_t = a.apply ? opt_lr_t(a.h, *a.iterations) : 0.f;
+  OptHyper h = a.h;
+  // the step kernel has advanced `iterations`: this update is the (iterations - 1)-th ever applied (tde_sched.h)
+  if constexpr (SCHED) h.lr = sched_lr(a.sched, *a.iterations - 1);
+  const float lr_t = SCHED ? opt_lr_t(h, *a.iterations) : a.apply ? opt_lr_t(a.h, *a.iterations) : 0.f;
   if (blk == 0) {  // metrics: loss sum, correct, count
     float ls = 0.f, cs = 0.f;
     for (int b = tid; b < a.B; b += 256) {
@@ -1119,6 +1140,8 @@ __device__ __forceinline__ void sn_wgrad(const SnWgradArgs a) {
     }
     // nothing writes `iterations` during this launch, so the next step kernel's workgroups all read one value
     if (tid == 0 && a.step) a.step[0] = a.iterations[0];
+    if constexpr (SCHED)
+      if (tid == 0 && a.lr_out) *a.lr_out = h.lr;
     return;
   }
   if (blk < a.conv_blk0 + a.conv_nblk) {  // conv partials: 32 parameters x 8 image slices
@@ -1137,7 +1160,7 @@ __device__ __forceinline__ void sn_wgrad(const SnWgradArgs a) {
       for (int k = 0; k < 8; ++k) sum += red[k][pp];
       for (int r = 0; r < a.nr; ++r) {
         if (p >= a.r[r].part_lo && p < a.r[r].part_lo + a.r[r].n) {
-          sn_commit<EXT>(a, a.r[r].flat_off + p - a.r[r].part_lo, sum, lr_t);
+          sn_commit<EXT, SCHED>(a, h, a.r[r].flat_off + p - a.r[r].part_lo, sum, lr_t);
           break;
         }
       }
@@ -1183,9 +1206,9 @@ __device__ __forceinline__ void sn_wgrad(const SnWgradArgs a) {
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
       const int i = i0 + 4 * fq + ii;
-      if (i < D.In) sn_commit<EXT>(a, D.w_off + i * D.Co + j0 + fr, acc[ii], lr_t);
+      if (i < D.In) sn_commit<EXT, SCHED>(a, h, D.w_off + i * D.Co + j0 + fr, acc[ii], lr_t);
     }
-    if (bias && fq == 0) sn_commit<EXT>(a, D.b_off + j0 + fr, accb[0], lr_t);
+    if (bias && fq == 0) sn_commit<EXT, SCHED>(a, h, D.b_off + j0 + fr, accb[0], lr_t);
   }
 }
 
@@ -1195,6 +1218,10 @@ __global__ __launch_bounds__(256) void smallnet_wgrad_kernel(SnWgradArgs a) {
 
 __global__ __launch_bounds__(256) void smallnet_wgrad_ext_kernel(SnWgradArgs a) {
   sn_wgrad<true>(a);
+}
+
+__global__ __launch_bounds__(256) void smallnet_wgrad_sched_kernel(SnWgradSchedArgs a) {
+  sn_wgrad<true, true>(a);
 }
 
 }  // namespace tde
@@ -1288,10 +1315,12 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
 // gradients into g; apply = 1 applies the optimizer (kind 0..5, lr, mom, b1, b2, eps) to w / m / v
 // (RMSprop: m = rms, v = the momentum accumulator of kind 5; an unknown kind or a missing slot returns -2).
 // step (optional): device word that block 0 sets to *iterations, the step index of the next step's masks.
-TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
-                               const float* part, int npart, const float* rec, int nrec, float* w, float* g, float* m,
-                               float* v, const long long* iterations, long long* step, float* metrics, int apply,
-                               int kind, float lr, float mom, float b1, float b2, float eps, hipStream_t stream) {
+// sched (nullable): the learning-rate schedule of tde_smallnet_wgrad_sched, its rate stored to lr_out.
+static int sn_wgrad_launch(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
+                           const float* part, int npart, const float* rec, int nrec, float* w, float* g, float* m,
+                           float* v, const long long* iterations, long long* step, float* metrics, int apply,
+                           int kind, float lr, float mom, float b1, float b2, float eps, const LrSched* sched,
+                           float* lr_out, hipStream_t stream) {
   if (nr > 2 * kSnMaxLayers || nd > kSnMaxLayers || B <= 0) return -1;
   if (step && !iterations) return -2;
   if (apply && (!opt_kind_known(kind) || !iterations || !opt_slots_ok(kind, m, v))) return -2;
@@ -1323,8 +1352,38 @@ TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int 
   a.step = step;
   a.metrics = metrics;
   a.h = OptHyper{kind, lr, mom, b1, b2, eps};
-  if (apply && !opt_kind_fused(kind)) smallnet_wgrad_ext_kernel<<<nblk, 256, 0, stream>>>(a);
-  else smallnet_wgrad_kernel<<<nblk, 256, 0, stream>>>(a);
+  if (sched) {
+    SnWgradSchedArgs sa{};
+    static_cast<SnWgradArgs&>(sa) = a;
+    sa.sched = *sched;
+    sa.lr_out = lr_out;
+    smallnet_wgrad_sched_kernel<<<nblk, 256, 0, stream>>>(sa);
+  } else if (apply && !opt_kind_fused(kind)) {
+    smallnet_wgrad_ext_kernel<<<nblk, 256, 0, stream>>>(a);
+  } else {
+    smallnet_wgrad_kernel<<<nblk, 256, 0, stream>>>(a);
+  }
   TDE_LAUNCH_CHECK();
   return 0;
+}
+
+TDE_API int tde_smallnet_wgrad(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
+                               const float* part, int npart, const float* rec, int nrec, float* w, float* g, float* m,
+                               float* v, const long long* iterations, long long* step, float* metrics, int apply,
+                               int kind, float lr, float mom, float b1, float b2, float eps, hipStream_t stream) {
+  return sn_wgrad_launch(ranges, nr, dense, nd, conv_nblk, B, part, npart, rec, nrec, w, g, m, v, iterations, step,
+                         metrics, apply, kind, lr, mom, b1, b2, eps, nullptr, nullptr, stream);
+}
+
+// The in-step update (apply = 1 always) of any kind 0..5 under a learning-rate schedule: the launch evaluates
+// `sched` (an LrSched, tde_sched.h) at *iterations - 1 in its prologue, uses that rate in place of h.lr (Adam's
+// step size is built from it) and stores it to lr_out (nullable).  A null or malformed schedule returns -4.
+TDE_API int tde_smallnet_wgrad_sched(const int* ranges, int nr, const int* dense, int nd, int conv_nblk, int B,
+                                     const float* part, int npart, const float* rec, int nrec, float* w, float* m,
+                                     float* v, const long long* iterations, long long* step, float* metrics,
+                                     int kind, float mom, float b1, float b2, float eps, const void* sched,
+                                     float* lr_out, hipStream_t stream) {
+  if (!sched || !sched_ok(*(const LrSched*)sched)) return -4;
+  return sn_wgrad_launch(ranges, nr, dense, nd, conv_nblk, B, part, npart, rec, nrec, w, nullptr, m, v, iterations,
+                         step, metrics, 1, kind, 0.f, mom, b1, b2, eps, (const LrSched*)sched, lr_out, stream);
 }

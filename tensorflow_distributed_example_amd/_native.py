@@ -55,6 +55,8 @@ _HIP_PROTOS = {
     "tde_optim_build_table": (i32, [p, i32, p]),
     "tde_optim_apply": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, p]),
     "tde_shadow_refresh": (i32, [p, p, p, p, i32, p]),
+    "tde_lr_schedule": (i32, [p, p, i64, p, p]),
+    "tde_sched_abi_sizes": (i32, [p, i32]),
     # layer-wise kernel library (csrc/kernels/layers.hip)
     "tde_igemm": (i32, [p, i64, i32, p, i64, i32, i32, i32, i32, p, i32, p, i64, i32, f32, p, i64, i32, p, i32,
                         p, p, p, p]),
@@ -113,6 +115,8 @@ _HIP_PROTOS = {
                                 p, p]),
     "tde_smallnet_wgrad": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p, i32, i32, f32, f32,
                                  f32, f32, f32, p]),
+    "tde_smallnet_wgrad_sched": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, i32, f32, f32,
+                                       f32, f32, p, p, p]),
     "tde_dgrad_phase_zero": (i32, [p, p, C.c_uint, p]),
     "tde_stem_unpack_wgrad": (i32, [p, p, p, p]),
     # RCCL

@@ -25,8 +25,42 @@ class OptHyper(_ct.Structure):
 
 
 def opt_hyper(optimizer):
+    """Under a learning-rate schedule ``lr`` is a placeholder (the schedule's first value): the launches that
+    take such an optimizer read the rate from the device (``lr_sched``)."""
     hp = optimizer.hparams()
-    return OptHyper(optimizer.kind_id, float(optimizer.learning_rate), hp["mom"], hp["b1"], hp["b2"], hp["eps"])
+    return OptHyper(optimizer.kind_id, float(optimizer.lr_at(0)), hp["mom"], hp["b1"], hp["b2"], hp["eps"])
+
+
+_SCHED_BOUNDS = 8
+
+
+class LrSched(_ct.Structure):
+    """``LrSched`` (csrc/include/tde_sched.h): a learning-rate schedule, evaluated on the device from the step
+    counter.  ``kind`` 0: none."""
+    _fields_ = [("kind", _ct.c_int), ("flags", _ct.c_int), ("lr0", _ct.c_float), ("p", _ct.c_float * 3),
+                ("decay_steps", _ct.c_longlong), ("nb", _ct.c_int), ("bound", _ct.c_longlong * _SCHED_BOUNDS),
+                ("val", _ct.c_float * (_SCHED_BOUNDS + 1))]
+
+
+def lr_sched(schedule):
+    """The descriptor of an ``optimizers.schedules.LearningRateSchedule``."""
+    d = schedule.descriptor()
+    _req(len(d["bounds"]) <= _SCHED_BOUNDS and (not d["values"] or len(d["values"]) == len(d["bounds"]) + 1),
+         f"a schedule descriptor carries at most {_SCHED_BOUNDS} boundaries")
+    s = LrSched(int(d["kind"]), int(d["flags"]), float(d["lr0"]), (_ct.c_float * 3)(*d["p"]), int(d["decay_steps"]),
+                len(d["bounds"]))
+    for i, b in enumerate(d["bounds"]):
+        s.bound[i] = int(b)
+    for i, v in enumerate(d["values"]):
+        s.val[i] = float(v)
+    return s
+
+
+def lr_schedule(sched: LrSched, iterations, bias, lr_out):
+    """``lr_out[0] = schedule(iterations[0] + bias)`` on the current stream (one wave)."""
+    _req(iterations.dtype == torch.int64 and lr_out.dtype == torch.float32, "lr_schedule: int64 counter, f32 word")
+    rc = N.hip().tde_lr_schedule(_ct.byref(sched), _P(iterations), int(bias), _P(lr_out), _s())
+    N.check(rc, "tde_lr_schedule")
 
 
 def opt_slots(store, optimizer):

@@ -8,12 +8,19 @@ parameter buffer (csrc/kernels/optim.hip) that also zeroes gradients, refreshes
 bf16 weight shadows and advances the device-resident ``iterations`` counter.
 ``apply_reference`` is the torch implementation of the same math (CPU backend
 and numerics oracle).
+
+``learning_rate`` is a float or a ``schedules.LearningRateSchedule`` (``schedules.py``): the update that
+is the k-th ever applied uses ``lr_at(k)``.  On the GPU a schedule is evaluated from the device counter
+inside the captured step (csrc/include/tde_sched.h), so ``key()`` holds its configuration, not a rate.
 """
 from __future__ import annotations
 
 import math
 
 import torch
+
+from . import schedules
+from .schedules import LearningRateSchedule
 
 KIND = {"sgd": 0, "momentum": 1, "nesterov": 2, "adam": 3, "rmsprop": 4, "rmsprop_momentum": 5}
 # kinds the fused step kernels, the xGMI all-reduce and the parameter server apply themselves (opt_step in
@@ -25,13 +32,37 @@ class Optimizer:
     kind = "sgd"
 
     def __init__(self, learning_rate=0.01, name=None):
-        self.learning_rate = float(learning_rate)
+        self.learning_rate = learning_rate
         self.name = name or type(self).__name__
         self.iterations = 0  # host mirror; device counter lives in the program
 
     @property
+    def learning_rate(self):
+        """A float, or the ``schedules.LearningRateSchedule`` object it was given (as in Keras)."""
+        return self._lr
+
+    @learning_rate.setter
+    def learning_rate(self, value):
+        if isinstance(value, dict) and "class_name" in value:   # get_config()'s form of a schedule
+            value = schedules.deserialize(value)
+        self._lr = value if isinstance(value, LearningRateSchedule) else float(value)
+
+    @property
     def lr(self):
         return self.learning_rate
+
+    @property
+    def schedule(self):
+        """The learning-rate schedule, or None under a constant rate."""
+        return self._lr if isinstance(self._lr, LearningRateSchedule) else None
+
+    def lr_at(self, step):
+        """The rate of the update that is the ``step``-th ever applied (0 for the first)."""
+        return self._lr(step) if isinstance(self._lr, LearningRateSchedule) else self._lr
+
+    def current_lr(self):
+        """``lr_at`` at the host mirror of the step counter: the rate the next update uses."""
+        return self.lr_at(self.iterations)
 
     @property
     def kind_id(self):
@@ -46,13 +77,16 @@ class Optimizer:
     def key(self):
         """Everything a kernel argument struct holds of this optimizer: a plan that built its structs at one
         key rebuilds them when the key has changed (compared for equality only, never stored)."""
-        return (self.kind_id, float(self.learning_rate), tuple(sorted(self.hparams().items())))
+        sch = self.schedule
+        # a schedule's key is its configuration: constant over the run, so nothing is captured again
+        return (self.kind_id, sch.key() if sch is not None else self._lr, tuple(sorted(self.hparams().items())))
 
     def apply_reference(self, w, g, slots, step):
         raise NotImplementedError
 
     def get_config(self):
-        return {"name": self.name, "learning_rate": self.learning_rate}
+        sch = self.schedule
+        return {"name": self.name, "learning_rate": schedules.serialize(sch) if sch is not None else self._lr}
 
 
 class SGD(Optimizer):
@@ -78,7 +112,7 @@ class SGD(Optimizer):
 
     @torch.no_grad()
     def apply_reference(self, w, g, slots, step):
-        lr = self.learning_rate
+        lr = self.lr_at(step)
         if self.momentum == 0.0:
             w.sub_(lr * g)
             return
@@ -119,7 +153,7 @@ class Adam(Optimizer):
         m, v = slots["m"], slots["v"]
         m.mul_(self.beta_1).add_((1 - self.beta_1) * g)
         v.mul_(self.beta_2).add_((1 - self.beta_2) * g * g)
-        lr_t = self.learning_rate * math.sqrt(1 - self.beta_2 ** t) / (1 - self.beta_1 ** t)
+        lr_t = self.lr_at(step) * math.sqrt(1 - self.beta_2 ** t) / (1 - self.beta_1 ** t)
         w.sub_(lr_t * m / (v.sqrt() + self.epsilon))
 
     def get_config(self):
@@ -156,7 +190,7 @@ class RMSprop(Optimizer):
 
     @torch.no_grad()
     def apply_reference(self, w, g, slots, step):
-        lr, r = self.learning_rate, slots["rms"]
+        lr, r = self.lr_at(step), slots["rms"]
         r.mul_(self.rho).add_((1 - self.rho) * g * g)
         if self.momentum > 0:
             q = slots["momentum"]

@@ -201,8 +201,14 @@ class PSClient:
                 gstep, ticket = so.value, to.value
         return gstep, ticket
 
-    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7):
-        """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms)."""
+    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7, learning_rate=None):
+        """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms).
+        ``learning_rate`` (optional) is only checked: the rate itself travels with every push."""
+        from ..schedules import LearningRateSchedule
+        if isinstance(learning_rate, LearningRateSchedule):
+            raise ValueError(f"the parameter server takes a constant learning rate (got the schedule "
+                             f"{type(learning_rate).__name__}; a learning-rate schedule is not supported under "
+                             "ParameterServerStrategy)")
         if int(kind) not in FUSED_KINDS:
             raise ValueError(f"the parameter server applies optimizer kinds 0..3 only (got kind {kind}; RMSprop "
                              "is not supported under ParameterServerStrategy)")

@@ -182,6 +182,44 @@ class ProfilerCallback(Callback):
         self._hook.after_step(_Ctx)
 
 
+class LearningRateScheduler(Callback):
+    """``tf.keras.callbacks.LearningRateScheduler(schedule, verbose=0)``: at the beginning of every epoch
+    ``optimizer.learning_rate = schedule(epoch, lr)``, a host function; the epoch's logs gain ``lr``.
+
+    A changed rate changes ``optimizer.key()``, so the step is captured again, once per epoch.  The per-step
+    form, evaluated on the device inside the captured step and never captured again, is a schedule object
+    (``optimizers.schedules``) given to the optimizer as its ``learning_rate``."""
+
+    def __init__(self, schedule, verbose=0):
+        super().__init__()
+        self.schedule = schedule
+        self.verbose = verbose
+
+    def on_epoch_begin(self, epoch, logs=None):
+        opt = self.model.optimizer
+        if opt.schedule is not None:
+            raise ValueError("LearningRateScheduler sets a constant rate per epoch; the optimizer's learning_rate "
+                             f"is the schedule {type(opt.schedule).__name__}")
+        try:
+            lr = self.schedule(epoch, opt.learning_rate)
+        except TypeError:   # the older one-argument form, schedule(epoch)
+            lr = self.schedule(epoch)
+        if not isinstance(lr, (int, float)):
+            raise ValueError(f"the schedule function must return a float (got {lr!r})")
+        opt.learning_rate = float(lr)
+        if self.verbose:
+            print(f"\nEpoch {epoch + 1}: LearningRateScheduler setting learning rate to {float(lr)}.")
+
+    def on_epoch_end(self, epoch, logs=None):
+        lr = float(self.model.optimizer.learning_rate)
+        if logs is not None:
+            logs["lr"] = lr
+        # fit() puts its History first in the callback list: it has recorded this epoch's logs already
+        hist = getattr(self.model, "history", None)
+        if hist is not None and len(hist.history.get("lr", ())) < len(hist.epoch):
+            hist.history.setdefault("lr", []).append(lr)
+
+
 class LambdaCallback(Callback):
     def __init__(self, on_epoch_end=None, on_train_batch_end=None, **kw):
         super().__init__()

@@ -262,6 +262,11 @@ class Estimator:
                 # Nesterov / Adam only: refuse before a connection is opened
                 raise ValueError(f"ParameterServerStrategy does not support the optimizer {opt.name} "
                                  f"({opt.kind}): the parameter server applies SGD, momentum, Nesterov or Adam")
+            if opt is not None and opt.schedule is not None:
+                # the rate travels with every push as a host float; the ps tasks know no step-dependent rate
+                raise ValueError(f"ParameterServerStrategy does not support the learning-rate schedule "
+                                 f"{type(opt.schedule).__name__} of {opt.name}: the parameter server takes a "
+                                 "constant learning rate")
             return self._train_ps(st, input_fn, hooks, steps, max_steps, saving_listeners)
         return self._train_sync(st, input_fn, hooks, steps, max_steps, saving_listeners)
 
@@ -380,7 +385,7 @@ class Estimator:
             self._psc = strategy.client(shapes)
             hp = m.optimizer.hparams()
             self._psc.set_optimizer(m.optimizer.kind_id, momentum=hp["mom"], beta1=hp["b1"], beta2=hp["b2"],
-                                    epsilon=hp["eps"])
+                                    epsilon=hp["eps"], learning_rate=m.optimizer.learning_rate)
         return self._psc
 
     def _train_ps(self, strategy, input_fn, hooks, steps, max_steps, saving_listeners):

@@ -101,7 +101,10 @@ class ReplicaPlan:
         """The optimizer is one the fused step kernels and the xGMI all-reduce apply themselves (kinds 0..3,
         ``opt_step``).  RMSprop is not: such a plan runs "plain", the multi-tensor launch applies it."""
         from ..optimizers import FUSED_KINDS
-        return self.optimizer is not None and self.optimizer.kind_id in FUSED_KINDS
+        # a learning-rate schedule takes the same route: those kernels carry the rate by value, the
+        # multi-tensor launch reads it from the device word the schedule launch wrote (OptimizerKernel)
+        return (self.optimizer is not None and self.optimizer.kind_id in FUSED_KINDS
+                and self.optimizer.schedule is None)
 
     def set_step_mode(self, mode):
         if not self.supports_step_mode(mode):
@@ -256,7 +259,13 @@ class ReferencePlan(ReplicaPlan):
 
 # ---------------------------------------------------------------------------------------
 class OptimizerKernel:
-    """Device-side state for the multi-tensor optimizer kernel of one replica."""
+    """Device-side state for the multi-tensor optimizer kernel of one replica.  Under a learning-rate schedule
+    it owns the device word ``lr_word``: ``apply()`` first launches the schedule at ``iterations + sched_bias``
+    into it, and the optimizer launch reads the rate from there, both on the step's stream (inside its capture)."""
+
+    # the step kernels have advanced ``iterations`` by the time ``apply()`` runs: the update is number
+    # iterations - 1 (csrc/include/tde_sched.h)
+    sched_bias = -1
 
     def __init__(self, store: P.ParamStore, optimizer, shadows: dict, iterations):
         from .. import _native as N
@@ -300,6 +309,10 @@ class OptimizerKernel:
         self.nblocks = nb
         self.segs_dev = torch.from_numpy(arr.view(np.uint8).copy()).to(store.device)
         self.table_dev = torch.from_numpy(table).to(store.device)
+        self.lr_word = None
+        if optimizer.schedule is not None:
+            self.lr_word = torch.full((1,), float(optimizer.lr_at(0)), dtype=torch.float32, device=store.device)
+        self._sched = self._sched_key = None
         self.refresh_shadows()
 
     def refresh_shadows(self):
@@ -318,10 +331,19 @@ class OptimizerKernel:
         from ..ops.kernels import opt_hyper, opt_slots
         h = opt_hyper(self.optimizer)
         m, v = opt_slots(st, self.optimizer)
+        sch = self.optimizer.schedule
+        if sch is not None:
+            from ..ops import kernels as K
+            if self.lr_word is None:   # the optimizer was given a schedule after this plan was built
+                self.lr_word = torch.zeros(1, dtype=torch.float32, device=st.device)
+            if self._sched_key != sch.key():
+                self._sched, self._sched_key = K.lr_sched(sch), sch.key()
+            K.lr_schedule(self._sched, self.iterations, self.sched_bias, self.lr_word)
         rc = N.hip().tde_optim_apply(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v), self.shadow.data_ptr(),
                                      self.segs_dev.data_ptr(), self.table_dev.data_ptr(), self.nblocks,
                                      self.iterations.data_ptr(), h.kind, h.lr, h.mom, h.b1, h.b2, h.eps, 1.0,
-                                     int(zero_grad), None, N.stream_ptr())
+                                     int(zero_grad), N.ptr(self.lr_word) if sch is not None else None,
+                                     N.stream_ptr())
         N.check(rc, "tde_optim_apply")
 
 

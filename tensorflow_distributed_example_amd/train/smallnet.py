@@ -31,6 +31,7 @@ Replaces the layer-wise plan's ~20 launches per LeNet-5 step (``train/layerwise.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import numpy as np
@@ -39,7 +40,7 @@ import torch
 from .. import _native as N
 from ..losses import SparseCategoricalCrossentropy
 from ..models import layers as L
-from ..ops.kernels import OptHyper, opt_hyper, opt_slots
+from ..ops.kernels import OptHyper, lr_sched, opt_hyper, opt_slots
 from .elementwise_ids import dropout_ids
 from .program import OptimizerKernel, ReplicaPlan
 
@@ -264,6 +265,7 @@ class SmallNetPlan(ReplicaPlan):
         # increments ``iterations`` while its grid runs, so it reads this word instead, which the weight
         # gradient launch sets to ``iterations`` for the next step.
         self.step_word = self.iterations.clone() if self.drops else None
+        self._sched = self._sched_key = None   # LrSched of the optimizer's schedule (step mode "local")
         self.stamps = None       # int64[64] to record workgroup 0's phase clock (bench/smallnet_phases.py)
 
     # ------------------------------------------------------------------ step modes
@@ -305,6 +307,20 @@ class SmallNetPlan(ReplicaPlan):
         st, opt = self.store, self.optimizer
         m, v = opt_slots(st, opt) if local else (None, None)
         h = opt_hyper(opt) if local else OptHyper()
+        if local and opt.schedule is not None:
+            # the launch evaluates the schedule at the device step counter itself and leaves the rate in the
+            # optimizer kernel's word (where the "plain" route keeps it)
+            if self._sched_key != opt.schedule.key():
+                self._sched, self._sched_key = lr_sched(opt.schedule), opt.schedule.key()
+            if self.opt.lr_word is None:
+                self.opt.lr_word = torch.zeros(1, dtype=torch.float32, device=self.device)
+            rc = self.lib.tde_smallnet_wgrad_sched(
+                self.ranges.ctypes.data, self.nranges, self.dense.ctypes.data, len(self.dense), self.conv_nblk, B,
+                self.part.data_ptr(), self.npart, self.rec.data_ptr(), self.nrec, st.w.data_ptr(), N.ptr(m), N.ptr(v),
+                self.iterations.data_ptr(), N.ptr(self.step_word), self.metrics.data_ptr(), h.kind, h.mom, h.b1, h.b2,
+                h.eps, ctypes.byref(self._sched), self.opt.lr_word.data_ptr(), N.stream_ptr())
+            N.check(rc, "tde_smallnet_wgrad_sched")
+            return
         rc = self.lib.tde_smallnet_wgrad(
             self.ranges.ctypes.data, self.nranges, self.dense.ctypes.data, len(self.dense), self.conv_nblk, B,
             self.part.data_ptr(), self.npart, self.rec.data_ptr(), self.nrec, st.w.data_ptr(), st.g.data_ptr(),
