@@ -14,16 +14,13 @@
 // cross-workgroup protocol.
 //
 // Vectorised: float4 loads/stores everywhere (segments are 256-byte aligned).
+//
+// CLIP variants (tde_optim_apply_clip): the gradient clipped (tde_clip.h) before the step, by value with c
+// in the arguments or by the scale the norm launches (gradclip.hip) left on the device.
+#include "tde_clip.h"
 #include "tde_optim.h"
 
 namespace tde {
-
-struct OptSeg {
-  long long off;      // element offset in the flat buffers
-  int rows, cols;     // logical 2-D shape (rows*cols elements)
-  long long sh_off;   // bf16 row-major shadow offset or -1
-  long long sht_off;  // bf16 transposed shadow offset or -1 (tiled blocks)
-};
 
 struct OptArgs {
   float* w; float* g; float* m; float* v;
@@ -40,31 +37,53 @@ struct OptArgs {
 constexpr int kChunk = 2048;
 constexpr int kTileR = 16;  // rows per transposed-shadow tile (tile = kTileR x 64)
 
-// The hyper-parameters in effect (lr_ptr applied) and the step size.
+// What a CLIP variant adds to OptArgs.
+struct ClipArgs {
+  const float* scale;   // norm modes: scale[seg] (kClipNorm) or scale[0] (kClipGlobalNorm)
+  float c;              // kClipValue: the bound
+  int mode;
+};
+
+// The hyper-parameters in effect (lr_ptr applied) and the step size; CLIP variants: the clip in effect for
+// this workgroup's segment (cs: the scale of a norm mode, else 1; cv: the bound of kClipValue, else +inf).
 struct Hyper {
   OptHyper oh;
   float lr_t;
+  float cs, cv;
 };
+
+// The gradient the step sees: g * grad_scale; CLIP: (g * grad_scale) * scale, or clamped to [-c, c], in one
+// straight line for both modes (the scale is 1 under kClipValue, the bound infinite under a norm mode, both
+// exact; the compares leave a NaN as the formulas do).
+template <bool CLIP>
+__device__ __forceinline__ float grad_eff(const OptArgs& a, float g, const Hyper& h) {
+  const float x = g * a.grad_scale;
+  if constexpr (CLIP) {
+    const float y = x * h.cs;
+    return y < -h.cv ? -h.cv : (y > h.cv ? h.cv : y);
+  }
+  return x;
+}
 
 // EXT = false: kinds 0..3 (the instruction stream these kinds always had).  EXT = true: the RMSprop kinds,
 // launched for kinds 4 / 5 only: rms is `m`, the momentum accumulator `v` (kind 5 alone reads or writes it).
-template <bool EXT>
+template <bool EXT, bool CLIP>
 __device__ __forceinline__ float upd1(const OptArgs& a, float w, float g, float& m, float& v, const Hyper& h) {
-  return opt_step<EXT>(h.oh, h.lr_t, w, g * a.grad_scale, m, v);
+  return opt_step<EXT>(h.oh, h.lr_t, w, grad_eff<CLIP>(a, g, h), m, v);
 }
 
 // Update 4 consecutive elements at flat index i (16-byte aligned).
-template <bool EXT>
+template <bool EXT, bool CLIP>
 __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& h) {
   float4 w = *reinterpret_cast<float4*>(a.w + i);
   const float4 g = *reinterpret_cast<float4*>(a.g + i);
   float4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
   if (opt_has_m<EXT>(a.h.kind)) m = *reinterpret_cast<float4*>(a.m + i);
   if (opt_has_v<EXT>(a.h.kind)) v = *reinterpret_cast<float4*>(a.v + i);
-  w.x = upd1<EXT>(a, w.x, g.x, m.x, v.x, h);
-  w.y = upd1<EXT>(a, w.y, g.y, m.y, v.y, h);
-  w.z = upd1<EXT>(a, w.z, g.z, m.z, v.z, h);
-  w.w = upd1<EXT>(a, w.w, g.w, m.w, v.w, h);
+  w.x = upd1<EXT, CLIP>(a, w.x, g.x, m.x, v.x, h);
+  w.y = upd1<EXT, CLIP>(a, w.y, g.y, m.y, v.y, h);
+  w.z = upd1<EXT, CLIP>(a, w.z, g.z, m.z, v.z, h);
+  w.w = upd1<EXT, CLIP>(a, w.w, g.w, m.w, v.w, h);
   *reinterpret_cast<float4*>(a.w + i) = w;
   if (a.zero_grad) *reinterpret_cast<float4*>(a.g + i) = float4{0.f, 0.f, 0.f, 0.f};
   if (opt_has_m<EXT>(a.h.kind)) *reinterpret_cast<float4*>(a.m + i) = m;
@@ -72,22 +91,27 @@ __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& 
   return w;
 }
 
-template <bool EXT>
+template <bool EXT, bool CLIP>
 __device__ __forceinline__ float upds(const OptArgs& a, size_t i, const Hyper& h) {
-  const float w = opt_step_at<EXT>(h.oh, h.lr_t, a.w, a.m, a.v, i, a.g[i] * a.grad_scale);
+  const float w = opt_step_at<EXT>(h.oh, h.lr_t, a.w, a.m, a.v, i, grad_eff<CLIP>(a, a.g[i], h));
   if (a.zero_grad) a.g[i] = 0.f;
   return w;
 }
 
-template <bool EXT>
-__device__ __forceinline__ void optim_apply(const OptArgs a) {
+template <bool EXT, bool CLIP>
+__device__ __forceinline__ void optim_apply(const OptArgs a, const ClipArgs k) {
   __shared__ bf16 tile[kTileR][72];
   const int4 ent = a.table[blockIdx.x];
   const OptSeg s = a.segs[ent.x];
-  Hyper h{a.h, 0.f};
+  Hyper h{a.h, 0.f, 1.f, __builtin_inff()};
   if (a.lr_ptr) h.oh.lr = *a.lr_ptr;
+  if constexpr (CLIP) {   // loaded in the round trip of lr_ptr and iterations
+    if (k.mode == kClipValue) h.cv = k.c;
+    else h.cs = k.scale[k.mode == kClipGlobalNorm ? 0 : ent.x];
+  }
   h.lr_t = opt_lr_t(h.oh, opt_uses_t(a.h.kind) ? *a.iterations : 0);
   const int tid = threadIdx.x;
+
 
   if (ent.y == 0) {
     const long long n = (long long)s.rows * s.cols;
@@ -97,14 +121,14 @@ __device__ __forceinline__ void optim_apply(const OptArgs a) {
     for (int it = 0; it < kChunk / 1024; ++it) {
       const long long e = beg + it * 1024 + tid * 4;
       if (e + 4 <= end) {
-        const float4 w = upd4<EXT>(a, (size_t)(s.off + e), h);
+        const float4 w = upd4<EXT, CLIP>(a, (size_t)(s.off + e), h);
         if (s.sh_off >= 0) {
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
         }
       } else {
         for (long long q = e; q < end && q < e + 4; ++q) {
-          const float w = upds<EXT>(a, (size_t)(s.off + q), h);
+          const float w = upds<EXT, CLIP>(a, (size_t)(s.off + q), h);
           if (s.sh_off >= 0) a.shadow[s.sh_off + q] = f2bf(w);
         }
       }
@@ -120,13 +144,13 @@ __device__ __forceinline__ void optim_apply(const OptArgs a) {
       if (gr < s.rows) {
         const long long e = (long long)gr * s.cols + gc;
         if (vec && gc + 4 <= s.cols) {
-          const float4 w = upd4<EXT>(a, (size_t)(s.off + e), h);
+          const float4 w = upd4<EXT, CLIP>(a, (size_t)(s.off + e), h);
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           if (s.sh_off >= 0) *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
           *reinterpret_cast<bf16x4*>(&tile[r][c]) = hv;
         } else {
           for (int q = 0; q < 4 && gc + q < s.cols; ++q) {
-            const float w = upds<EXT>(a, (size_t)(s.off + e + q), h);
+            const float w = upds<EXT, CLIP>(a, (size_t)(s.off + e + q), h);
             const bf16 hv = f2bf(w);
             if (s.sh_off >= 0) a.shadow[s.sh_off + e + q] = hv;
             tile[r][c + q] = hv;
@@ -144,12 +168,33 @@ __device__ __forceinline__ void optim_apply(const OptArgs a) {
   }
 }
 
+// The CLIP kernels.  A norm within c (scale exactly 1): nothing is clipped in this workgroup's segment, and
+// it runs the unclipped kernel's own program text, so its result is that kernel's bit for bit.  (Multiplying
+// by 1 is exact, but the compiler contracts opt_step's multiplies and adds differently around it: with the
+// multiply in place the RMSprop kinds came out one bit off on some elements.)  The choice needs the table
+// entry and the scale ahead of the prologue's other loads; both are read again there from the cache.
+template <bool EXT>
+__device__ __forceinline__ void optim_apply_clip(const OptArgs a, const ClipArgs k) {
+  if (k.mode != kClipValue && k.scale[k.mode == kClipGlobalNorm ? 0 : a.table[blockIdx.x].x] == 1.f)
+    optim_apply<EXT, false>(a, ClipArgs{});
+  else
+    optim_apply<EXT, true>(a, k);
+}
+
 __global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
-  optim_apply<false>(a);
+  optim_apply<false, false>(a, ClipArgs{});
 }
 
 __global__ __launch_bounds__(256) void optim_apply_ext_kernel(OptArgs a) {
-  optim_apply<true>(a);
+  optim_apply<true, false>(a, ClipArgs{});
+}
+
+__global__ __launch_bounds__(256) void optim_apply_clip_kernel(OptArgs a, ClipArgs k) {
+  optim_apply_clip<false>(a, k);
+}
+
+__global__ __launch_bounds__(256) void optim_apply_ext_clip_kernel(OptArgs a, ClipArgs k) {
+  optim_apply_clip<true>(a, k);
 }
 
 // Writes bf16 shadows from the current weights without updating (init/restore).
@@ -266,6 +311,31 @@ TDE_API int tde_optim_apply(float* w, float* g, float* m, float* v, void* shadow
             iterations, OptHyper{kind, lr, mom, b1, b2, eps}, grad_scale, zero_grad, lr_ptr};
   if (opt_kind_fused(kind)) optim_apply_kernel<<<nblocks, 256, 0, stream>>>(a);
   else optim_apply_ext_kernel<<<nblocks, 256, 0, stream>>>(a);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// tde_optim_apply with the gradient clipped first: g_eff = (g * grad_scale) * scale, scale = clip_scale[0]
+// (kClipGlobalNorm) or clip_scale[seg] (kClipNorm), or g * grad_scale clamped to [-clip_c, clip_c]
+// (kClipValue).  An unknown mode, clip_c not positive and finite or a null clip_scale in a norm mode: -3;
+// otherwise tde_optim_apply's codes.  A refusal launches nothing and writes nothing.
+TDE_API int tde_optim_apply_clip(float* w, float* g, float* m, float* v, void* shadow,
+                                 const void* segs_dev, const void* table_dev, int nblocks,
+                                 const long long* iterations, int kind, float lr, float mom, float b1,
+                                 float b2, float eps, float grad_scale, int zero_grad,
+                                 const float* lr_ptr, int clip_mode, float clip_c, const float* clip_scale,
+                                 hipStream_t stream) {
+  if (!opt_kind_known(kind) || !opt_slots_ok(kind, m, v)) return -2;
+  if (!clip_mode_known(clip_mode)) return -3;
+  if (clip_mode == kClipValue ? !clip_c_ok(clip_c) : !clip_scale) return -3;
+  if (nblocks <= 0) return 0;
+  if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return -1;
+  if ((uintptr_t)clip_scale & 3) return -1;
+  OptArgs a{w, g, m, v, (bf16*)shadow, (const OptSeg*)segs_dev, (const int4*)table_dev,
+            iterations, OptHyper{kind, lr, mom, b1, b2, eps}, grad_scale, zero_grad, lr_ptr};
+  const ClipArgs k{clip_scale, clip_c, clip_mode};
+  if (opt_kind_fused(kind)) optim_apply_clip_kernel<<<nblocks, 256, 0, stream>>>(a, k);
+  else optim_apply_ext_clip_kernel<<<nblocks, 256, 0, stream>>>(a, k);
   TDE_LAUNCH_CHECK();
   return 0;
 }

@@ -54,6 +54,12 @@ _HIP_PROTOS = {
     "tde_optim_table_size": (i32, [p, i32]),
     "tde_optim_build_table": (i32, [p, i32, p]),
     "tde_optim_apply": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, p]),
+    "tde_optim_apply_clip": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, i32, f32,
+                                   p, p]),
+    "tde_clip_table_size": (i32, [p, i32]),
+    "tde_clip_build_table": (i32, [p, i32, p, p]),
+    "tde_clip_sumsq": (i32, [p, p, p, i32, p, p]),
+    "tde_clip_scale": (i32, [p, p, i32, i32, i32, f32, p, p, p]),
     "tde_shadow_refresh": (i32, [p, p, p, p, i32, p]),
     "tde_lr_schedule": (i32, [p, p, i64, p, p]),
     "tde_sched_abi_sizes": (i32, [p, i32]),

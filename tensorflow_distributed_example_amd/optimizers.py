@@ -12,6 +12,11 @@ and numerics oracle).
 ``learning_rate`` is a float or a ``schedules.LearningRateSchedule`` (``schedules.py``): the update that
 is the k-th ever applied uses ``lr_at(k)``.  On the GPU a schedule is evaluated from the device counter
 inside the captured step (csrc/include/tde_sched.h), so ``key()`` holds its configuration, not a rate.
+
+``clipvalue`` / ``clipnorm`` / ``global_clipnorm`` (at most one, as in Keras 3) clip the aggregated gradient
+before the update (TF 2.4+ order: after the all-reduce): ``clip_reference`` is the torch form, on the GPU two
+norm launches and a clipped variant of the multi-tensor launch run inside the captured step
+(csrc/include/tde_clip.h).
 """
 from __future__ import annotations
 
@@ -26,15 +31,79 @@ KIND = {"sgd": 0, "momentum": 1, "nesterov": 2, "adam": 3, "rmsprop": 4, "rmspro
 # kinds the fused step kernels, the xGMI all-reduce and the parameter server apply themselves (opt_step in
 # csrc/include/tde_optim.h); the others run through the multi-tensor launch or the small-net commit only
 FUSED_KINDS = (0, 1, 2, 3)
+# optimizer.clip[0] -> the kernels' mode (csrc/include/tde_clip.h)
+CLIP_MODE = {"clipvalue": 1, "clipnorm": 2, "global_clipnorm": 3}
+
+
+def _clip_of(clipnorm, clipvalue, global_clipnorm):
+    given = [(k, v) for k, v in (("clipnorm", clipnorm), ("clipvalue", clipvalue),
+                                 ("global_clipnorm", global_clipnorm)) if v is not None]
+    if len(given) > 1:
+        raise ValueError("only one of clipnorm, clipvalue and global_clipnorm can be set (got "
+                         + ", ".join(f"{k}={v!r}" for k, v in given) + ")")
+    if not given:
+        return None
+    mode, c = given[0]
+    try:
+        c = float(c)
+    except (TypeError, ValueError):
+        raise ValueError(f"{mode} must be a positive finite float (got {given[0][1]!r})") from None
+    if not (c > 0.0 and math.isfinite(c)):
+        raise ValueError(f"{mode} must be a positive finite float (got {c!r})")
+    return mode, c
 
 
 class Optimizer:
     kind = "sgd"
 
-    def __init__(self, learning_rate=0.01, name=None):
+    def __init__(self, learning_rate=0.01, name=None, clipnorm=None, clipvalue=None, global_clipnorm=None, **kw):
+        if "lr" in kw:   # the Keras 2 spelling
+            learning_rate = kw.pop("lr")
+        if kw:
+            raise TypeError(f"{type(self).__name__}() got unexpected keyword argument(s) "
+                            + ", ".join(repr(k) for k in sorted(kw)))
         self.learning_rate = learning_rate
         self.name = name or type(self).__name__
         self.iterations = 0  # host mirror; device counter lives in the program
+        self._clip = _clip_of(clipnorm, clipvalue, global_clipnorm)
+
+    @property
+    def clip(self):
+        """None, or (mode, c) with mode "clipvalue", "clipnorm" or "global_clipnorm" (constructor-only)."""
+        return self._clip
+
+    @property
+    def clipvalue(self):
+        return self._clip[1] if self._clip and self._clip[0] == "clipvalue" else None
+
+    @property
+    def clipnorm(self):
+        return self._clip[1] if self._clip and self._clip[0] == "clipnorm" else None
+
+    @property
+    def global_clipnorm(self):
+        return self._clip[1] if self._clip and self._clip[0] == "global_clipnorm" else None
+
+    @torch.no_grad()
+    def clip_reference(self, g, segments):
+        """Clips the flat (aggregated) gradient ``g`` in place: ``segments`` are the (offset, numel) of the
+        trainable variables; what lies between them is left alone.  The kernels' order: each element times
+        the scale c / max(norm, c), a zero gradient scaled by exactly 1."""
+        if self._clip is None:
+            return g
+        mode, c = self._clip
+        views = [g[o: o + n] for o, n in segments]
+        if mode == "clipvalue":
+            for x in views:
+                x.clamp_(-c, c)
+            return g
+        sq = [x.double().square().sum() for x in views]
+        if mode == "global_clipnorm":
+            sq = [torch.stack(sq).sum()] * len(views) if views else []
+        for x, s in zip(views, sq):
+            norm = s.sqrt().to(g.dtype)
+            x.mul_(c / torch.clamp(norm, min=c))
+        return g
 
     @property
     def learning_rate(self):
@@ -79,20 +148,23 @@ class Optimizer:
         key rebuilds them when the key has changed (compared for equality only, never stored)."""
         sch = self.schedule
         # a schedule's key is its configuration: constant over the run, so nothing is captured again
-        return (self.kind_id, sch.key() if sch is not None else self._lr, tuple(sorted(self.hparams().items())))
+        return (self.kind_id, sch.key() if sch is not None else self._lr, tuple(sorted(self.hparams().items())),
+                self._clip)
 
     def apply_reference(self, w, g, slots, step):
         raise NotImplementedError
 
     def get_config(self):
         sch = self.schedule
-        return {"name": self.name, "learning_rate": schedules.serialize(sch) if sch is not None else self._lr}
+        cfg = {"name": self.name, "learning_rate": schedules.serialize(sch) if sch is not None else self._lr}
+        if self._clip is not None:   # the one that is set: ``type(opt)(**config)`` rebuilds the optimizer
+            cfg[self._clip[0]] = self._clip[1]
+        return cfg
 
 
 class SGD(Optimizer):
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, name="SGD", **kw):
-        lr = kw.pop("lr", learning_rate)
-        super().__init__(lr, name)
+        super().__init__(learning_rate, name, **kw)
         self.momentum = float(momentum)
         self.nesterov = bool(nesterov)
         if self.momentum < 0:
@@ -138,7 +210,7 @@ class Adam(Optimizer):
     kind = "adam"
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="Adam", **kw):
-        super().__init__(kw.pop("lr", learning_rate), name)
+        super().__init__(learning_rate, name, **kw)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
 
     def slot_names(self):
@@ -167,7 +239,7 @@ class RMSprop(Optimizer):
 
     def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, name="RMSprop",
                  **kw):
-        super().__init__(kw.pop("lr", learning_rate), name)
+        super().__init__(learning_rate, name, **kw)
         self.rho, self.momentum, self.epsilon = float(rho), float(momentum), float(epsilon)
         self.centered = bool(centered)
         if self.centered:

@@ -201,10 +201,15 @@ class PSClient:
                 gstep, ticket = so.value, to.value
         return gstep, ticket
 
-    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7, learning_rate=None):
+    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7, learning_rate=None, clip=None):
         """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms).
-        ``learning_rate`` (optional) is only checked: the rate itself travels with every push."""
+        ``learning_rate`` (optional) is only checked: the rate itself travels with every push.  ``clip``
+        (optional, ``optimizer.clip``) is only checked too: the ps tasks apply each push as it arrives."""
         from ..schedules import LearningRateSchedule
+        if clip is not None:
+            raise ValueError(f"the parameter server applies unclipped gradients (got {clip[0]}={clip[1]!r}; "
+                             "clipnorm, clipvalue and global_clipnorm are not supported under "
+                             "ParameterServerStrategy)")
         if isinstance(learning_rate, LearningRateSchedule):
             raise ValueError(f"the parameter server takes a constant learning rate (got the schedule "
                              f"{type(learning_rate).__name__}; a learning-rate schedule is not supported under "

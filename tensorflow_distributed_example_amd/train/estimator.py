@@ -267,6 +267,11 @@ class Estimator:
                 raise ValueError(f"ParameterServerStrategy does not support the learning-rate schedule "
                                  f"{type(opt.schedule).__name__} of {opt.name}: the parameter server takes a "
                                  "constant learning rate")
+            if opt is not None and opt.clip is not None:
+                # every push is applied by the ps tasks as it arrives: no norm over a whole gradient exists there
+                raise ValueError(f"ParameterServerStrategy does not support {opt.clip[0]}={opt.clip[1]!r} of "
+                                 f"{opt.name}: the parameter server applies unclipped gradients (clipnorm, "
+                                 "clipvalue and global_clipnorm need a synchronous strategy)")
             return self._train_ps(st, input_fn, hooks, steps, max_steps, saving_listeners)
         return self._train_sync(st, input_fn, hooks, steps, max_steps, saving_listeners)
 
@@ -385,7 +390,8 @@ class Estimator:
             self._psc = strategy.client(shapes)
             hp = m.optimizer.hparams()
             self._psc.set_optimizer(m.optimizer.kind_id, momentum=hp["mom"], beta1=hp["b1"], beta2=hp["b2"],
-                                    epsilon=hp["eps"], learning_rate=m.optimizer.learning_rate)
+                                    epsilon=hp["eps"], learning_rate=m.optimizer.learning_rate,
+                                    clip=m.optimizer.clip)
         return self._psc
 
     def _train_ps(self, strategy, input_fn, hooks, steps, max_steps, saving_listeners):

@@ -103,8 +103,10 @@ class ReplicaPlan:
         from ..optimizers import FUSED_KINDS
         # a learning-rate schedule takes the same route: those kernels carry the rate by value, the
         # multi-tensor launch reads it from the device word the schedule launch wrote (OptimizerKernel)
+        # gradient clipping too: a norm needs every gradient before any update, a grid-wide dependency the
+        # fused steps do not have; the norm launches run in front of the multi-tensor launch
         return (self.optimizer is not None and self.optimizer.kind_id in FUSED_KINDS
-                and self.optimizer.schedule is None)
+                and self.optimizer.schedule is None and self.optimizer.clip is None)
 
     def set_step_mode(self, mode):
         if not self.supports_step_mode(mode):
@@ -237,6 +239,9 @@ class ReferencePlan(ReplicaPlan):
     def apply(self):
         st = self.store
         slots = {n: st.slot(n) for n in self.optimizer.slot_names()}
+        if self.optimizer.clip is not None:   # st.g is the aggregated gradient by now: clipped after the all-reduce
+            segs = [(st.segments[n].offset, st.segments[n].numel) for n in st.names(trainable=True)]
+            self.optimizer.clip_reference(st.g, segs)
         self.optimizer.apply_reference(st.w, st.g, slots, int(self.iterations.item()))
         st.g.zero_()
         self.iterations += 1
@@ -313,6 +318,22 @@ class OptimizerKernel:
         if optimizer.schedule is not None:
             self.lr_word = torch.full((1,), float(optimizer.lr_at(0)), dtype=torch.float32, device=store.device)
         self._sched = self._sched_key = None
+        # gradient clipping (csrc/include/tde_clip.h): the sum-of-squares table and the words the norm launches
+        # write; clipvalue travels by value and needs none of them
+        self.clip_nent = 0
+        self.clip_ents_dev = self.clip_ranges_dev = self.clip_partials = self.clip_norm = self.clip_scale = None
+        if optimizer.clip is not None and optimizer.clip[0] != "clipvalue":
+            ne = lib.tde_clip_table_size(arr.ctypes.data, len(arr))
+            ents = np.zeros((max(ne, 1), 2), dtype=np.int32)
+            ranges = np.zeros((max(len(arr), 1), 2), dtype=np.int32)
+            lib.tde_clip_build_table(arr.ctypes.data, len(arr), ents.ctypes.data, ranges.ctypes.data)
+            self.clip_nent = ne
+            self.clip_ents_dev = torch.from_numpy(ents).to(store.device)
+            self.clip_ranges_dev = torch.from_numpy(ranges).to(store.device)
+            nw = len(arr) if optimizer.clip[0] == "clipnorm" else 1
+            self.clip_partials = torch.zeros(max(ne, 1), dtype=torch.float32, device=store.device)
+            self.clip_norm = torch.zeros(max(nw, 1), dtype=torch.float32, device=store.device)
+            self.clip_scale = torch.ones(max(nw, 1), dtype=torch.float32, device=store.device)
         self.refresh_shadows()
 
     def refresh_shadows(self):
@@ -339,6 +360,26 @@ class OptimizerKernel:
             if self._sched_key != sch.key():
                 self._sched, self._sched_key = K.lr_sched(sch), sch.key()
             K.lr_schedule(self._sched, self.iterations, self.sched_bias, self.lr_word)
+        lr_ptr = N.ptr(self.lr_word) if sch is not None else None
+        if self.optimizer.clip is not None:
+            from ..optimizers import CLIP_MODE
+            mode, c = CLIP_MODE[self.optimizer.clip[0]], float(self.optimizer.clip[1])
+            lib = N.hip()
+            if self.clip_scale is not None:   # a norm mode: partials, then norm and scale, on the step's stream
+                rc = lib.tde_clip_sumsq(st.g.data_ptr(), self.segs_dev.data_ptr(), self.clip_ents_dev.data_ptr(),
+                                        self.clip_nent, self.clip_partials.data_ptr(), N.stream_ptr())
+                N.check(rc, "tde_clip_sumsq")
+                rc = lib.tde_clip_scale(self.clip_partials.data_ptr(), self.clip_ranges_dev.data_ptr(),
+                                        len(self._segs_host), self.clip_nent, mode, c, self.clip_norm.data_ptr(),
+                                        self.clip_scale.data_ptr(), N.stream_ptr())
+                N.check(rc, "tde_clip_scale")
+            rc = lib.tde_optim_apply_clip(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v),
+                                          self.shadow.data_ptr(), self.segs_dev.data_ptr(),
+                                          self.table_dev.data_ptr(), self.nblocks, self.iterations.data_ptr(), h.kind,
+                                          h.lr, h.mom, h.b1, h.b2, h.eps, 1.0, int(zero_grad), lr_ptr, mode, c,
+                                          N.ptr(self.clip_scale), N.stream_ptr())
+            N.check(rc, "tde_optim_apply_clip")
+            return
         rc = N.hip().tde_optim_apply(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v), self.shadow.data_ptr(),
                                      self.segs_dev.data_ptr(), self.table_dev.data_ptr(), self.nblocks,
                                      self.iterations.data_ptr(), h.kind, h.lr, h.mom, h.b1, h.b2, h.eps, 1.0,

@@ -274,7 +274,10 @@ class SmallNetPlan(ReplicaPlan):
         # "xgmi": data parallel, the xGMI all-reduce applies the update to the f32 weights (kinds 0..3).
         if mode == "xgmi":
             return self._opt_fused() and self.device.type == "cuda"
-        return mode == "plain" or (mode == "local" and self.optimizer is not None and self.device.type == "cuda")
+        # A clipping optimizer runs "plain": a norm needs every gradient before any update, and the weight
+        # gradient launch updates each range as its gradient is finished.
+        return mode == "plain" or (mode == "local" and self.optimizer is not None and self.optimizer.clip is None
+                                   and self.device.type == "cuda")
 
     def set_iterations(self, step):
         super().set_iterations(step)
