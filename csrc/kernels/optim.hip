@@ -17,8 +17,12 @@
 //
 // CLIP variants (tde_optim_apply_clip): the gradient clipped (tde_clip.h) before the step, by value with c
 // in the arguments or by the scale the norm launches (gradclip.hip) left on the device.
+//
+// WD variants (tde_optim_apply_wd): decoupled weight decay (tde_reg.h) in front of the step, with or without
+// a clip: the step starts from w - (w * wd[seg]) * lr, lr the rate in effect (lr_ptr applied; never Adam's lr_t).
 #include "tde_clip.h"
 #include "tde_optim.h"
+#include "tde_reg.h"
 
 namespace tde {
 
@@ -44,13 +48,29 @@ struct ClipArgs {
   int mode;
 };
 
+// What a WD variant adds to OptArgs.
+struct WdArgs {
+  const float* wd;      // wd[seg]: the segment's decay, 0 for a variable excluded from it
+};
+
 // The hyper-parameters in effect (lr_ptr applied) and the step size; CLIP variants: the clip in effect for
-// this workgroup's segment (cs: the scale of a norm mode, else 1; cv: the bound of kClipValue, else +inf).
+// this workgroup's segment (cs: the scale of a norm mode, else 1; cv: the bound of kClipValue, else +inf);
+// WD variants: the segment's decay.
 struct Hyper {
   OptHyper oh;
   float lr_t;
   float cs, cv;
+  float wd;
 };
+
+// The weight a WD variant's step starts from: three roundings, product, product, difference, never
+// contracted into an fma (the host form f32(w - f32(f32(w * wd) * lr)) is what the tests feed the oracles).
+__device__ __forceinline__ float wd_start(float w, const Hyper& h) {
+#pragma clang fp contract(off)
+  const float d = w * h.wd;
+  const float e = d * h.oh.lr;
+  return w - e;
+}
 
 // The gradient the step sees: g * grad_scale; CLIP: (g * grad_scale) * scale, or clamped to [-c, c], in one
 // straight line for both modes (the scale is 1 under kClipValue, the bound infinite under a norm mode, both
@@ -73,13 +93,14 @@ __device__ __forceinline__ float upd1(const OptArgs& a, float w, float g, float&
 }
 
 // Update 4 consecutive elements at flat index i (16-byte aligned).
-template <bool EXT, bool CLIP>
+template <bool EXT, bool CLIP, bool WD>
 __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& h) {
   float4 w = *reinterpret_cast<float4*>(a.w + i);
   const float4 g = *reinterpret_cast<float4*>(a.g + i);
   float4 m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
   if (opt_has_m<EXT>(a.h.kind)) m = *reinterpret_cast<float4*>(a.m + i);
   if (opt_has_v<EXT>(a.h.kind)) v = *reinterpret_cast<float4*>(a.v + i);
+  if constexpr (WD) w = float4{wd_start(w.x, h), wd_start(w.y, h), wd_start(w.z, h), wd_start(w.w, h)};
   w.x = upd1<EXT, CLIP>(a, w.x, g.x, m.x, v.x, h);
   w.y = upd1<EXT, CLIP>(a, w.y, g.y, m.y, v.y, h);
   w.z = upd1<EXT, CLIP>(a, w.z, g.z, m.z, v.z, h);
@@ -91,20 +112,25 @@ __device__ __forceinline__ float4 upd4(const OptArgs& a, size_t i, const Hyper& 
   return w;
 }
 
-template <bool EXT, bool CLIP>
+template <bool EXT, bool CLIP, bool WD>
 __device__ __forceinline__ float upds(const OptArgs& a, size_t i, const Hyper& h) {
-  const float w = opt_step_at<EXT>(h.oh, h.lr_t, a.w, a.m, a.v, i, grad_eff<CLIP>(a, a.g[i], h));
+  float w;
+  if constexpr (WD)
+    w = opt_step_at<EXT>(h.oh, h.lr_t, wd_start(a.w[i], h), a.w, a.m, a.v, i, grad_eff<CLIP>(a, a.g[i], h));
+  else
+    w = opt_step_at<EXT>(h.oh, h.lr_t, a.w, a.m, a.v, i, grad_eff<CLIP>(a, a.g[i], h));
   if (a.zero_grad) a.g[i] = 0.f;
   return w;
 }
 
-template <bool EXT, bool CLIP>
-__device__ __forceinline__ void optim_apply(const OptArgs a, const ClipArgs k) {
+template <bool EXT, bool CLIP, bool WD = false>
+__device__ __forceinline__ void optim_apply(const OptArgs a, const ClipArgs k, const WdArgs d = WdArgs{}) {
   __shared__ bf16 tile[kTileR][72];
   const int4 ent = a.table[blockIdx.x];
   const OptSeg s = a.segs[ent.x];
-  Hyper h{a.h, 0.f, 1.f, __builtin_inff()};
+  Hyper h{a.h, 0.f, 1.f, __builtin_inff(), 0.f};
   if (a.lr_ptr) h.oh.lr = *a.lr_ptr;
+  if constexpr (WD) h.wd = d.wd[ent.x];   // in the round trip of lr_ptr and iterations
   if constexpr (CLIP) {   // loaded in the round trip of lr_ptr and iterations
     if (k.mode == kClipValue) h.cv = k.c;
     else h.cs = k.scale[k.mode == kClipGlobalNorm ? 0 : ent.x];
@@ -121,14 +147,14 @@ __device__ __forceinline__ void optim_apply(const OptArgs a, const ClipArgs k) {
     for (int it = 0; it < kChunk / 1024; ++it) {
       const long long e = beg + it * 1024 + tid * 4;
       if (e + 4 <= end) {
-        const float4 w = upd4<EXT, CLIP>(a, (size_t)(s.off + e), h);
+        const float4 w = upd4<EXT, CLIP, WD>(a, (size_t)(s.off + e), h);
         if (s.sh_off >= 0) {
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
         }
       } else {
         for (long long q = e; q < end && q < e + 4; ++q) {
-          const float w = upds<EXT, CLIP>(a, (size_t)(s.off + q), h);
+          const float w = upds<EXT, CLIP, WD>(a, (size_t)(s.off + q), h);
           if (s.sh_off >= 0) a.shadow[s.sh_off + q] = f2bf(w);
         }
       }
@@ -144,13 +170,13 @@ __device__ __forceinline__ void optim_apply(const OptArgs a, const ClipArgs k) {
       if (gr < s.rows) {
         const long long e = (long long)gr * s.cols + gc;
         if (vec && gc + 4 <= s.cols) {
-          const float4 w = upd4<EXT, CLIP>(a, (size_t)(s.off + e), h);
+          const float4 w = upd4<EXT, CLIP, WD>(a, (size_t)(s.off + e), h);
           bf16x4 hv = {f2bf(w.x), f2bf(w.y), f2bf(w.z), f2bf(w.w)};
           if (s.sh_off >= 0) *reinterpret_cast<bf16x4*>(a.shadow + s.sh_off + e) = hv;
           *reinterpret_cast<bf16x4*>(&tile[r][c]) = hv;
         } else {
           for (int q = 0; q < 4 && gc + q < s.cols; ++q) {
-            const float w = upds<EXT, CLIP>(a, (size_t)(s.off + e + q), h);
+            const float w = upds<EXT, CLIP, WD>(a, (size_t)(s.off + e + q), h);
             const bf16 hv = f2bf(w);
             if (s.sh_off >= 0) a.shadow[s.sh_off + e + q] = hv;
             tile[r][c + q] = hv;
@@ -181,6 +207,23 @@ __device__ __forceinline__ void optim_apply_clip(const OptArgs a, const ClipArgs
     optim_apply<EXT, true>(a, k);
 }
 
+// The WD kernels, with a clip (k.mode) or without (kClipNone).  A workgroup whose segment's decay is zero (a
+// variable excluded from it) runs the program text without the decay, clipped or not as above: bit for bit
+// what tde_optim_apply / tde_optim_apply_clip give that variable.
+template <bool EXT>
+__device__ __forceinline__ void optim_apply_wd(const OptArgs a, const ClipArgs k, const WdArgs d) {
+  const int seg = a.table[blockIdx.x].x;
+  const bool clip = k.mode == kClipValue ||
+                    (k.mode != kClipNone && k.scale[k.mode == kClipGlobalNorm ? 0 : seg] != 1.f);
+  if (d.wd[seg] != 0.f) {
+    if (clip) optim_apply<EXT, true, true>(a, k, d);
+    else optim_apply<EXT, false, true>(a, ClipArgs{}, d);
+  } else {
+    if (clip) optim_apply<EXT, true>(a, k);
+    else optim_apply<EXT, false>(a, ClipArgs{});
+  }
+}
+
 __global__ __launch_bounds__(256) void optim_apply_kernel(OptArgs a) {
   optim_apply<false, false>(a, ClipArgs{});
 }
@@ -195,6 +238,14 @@ __global__ __launch_bounds__(256) void optim_apply_clip_kernel(OptArgs a, ClipAr
 
 __global__ __launch_bounds__(256) void optim_apply_ext_clip_kernel(OptArgs a, ClipArgs k) {
   optim_apply_clip<true>(a, k);
+}
+
+__global__ __launch_bounds__(256) void optim_apply_wd_kernel(OptArgs a, ClipArgs k, WdArgs d) {
+  optim_apply_wd<false>(a, k, d);
+}
+
+__global__ __launch_bounds__(256) void optim_apply_ext_wd_kernel(OptArgs a, ClipArgs k, WdArgs d) {
+  optim_apply_wd<true>(a, k, d);
 }
 
 // Writes bf16 shadows from the current weights without updating (init/restore).
@@ -336,6 +387,35 @@ TDE_API int tde_optim_apply_clip(float* w, float* g, float* m, float* v, void* s
   const ClipArgs k{clip_scale, clip_c, clip_mode};
   if (opt_kind_fused(kind)) optim_apply_clip_kernel<<<nblocks, 256, 0, stream>>>(a, k);
   else optim_apply_ext_clip_kernel<<<nblocks, 256, 0, stream>>>(a, k);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// tde_optim_apply / tde_optim_apply_clip with decoupled weight decay in front of the step: the step of segment
+// s starts from w - (w * wd[s]) * lr, lr = *lr_ptr when given.  clip_mode kClipNone (0): no clip; otherwise
+// tde_optim_apply_clip's rules and codes.  A null wd: -3; wd off the 4-byte grid: -1.  The values of wd live
+// on the device: the caller checks them (finite, >= 0).  A refusal launches nothing and writes nothing.
+TDE_API int tde_optim_apply_wd(float* w, float* g, float* m, float* v, void* shadow,
+                               const void* segs_dev, const void* table_dev, int nblocks,
+                               const long long* iterations, int kind, float lr, float mom, float b1,
+                               float b2, float eps, float grad_scale, int zero_grad,
+                               const float* lr_ptr, int clip_mode, float clip_c, const float* clip_scale,
+                               const float* wd, hipStream_t stream) {
+  if (!opt_kind_known(kind) || !opt_slots_ok(kind, m, v)) return -2;
+  if (clip_mode != kClipNone) {
+    if (!clip_mode_known(clip_mode)) return -3;
+    if (clip_mode == kClipValue ? !clip_c_ok(clip_c) : !clip_scale) return -3;
+  }
+  if (!wd) return -3;
+  if (nblocks <= 0) return 0;
+  if (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return -1;
+  if (((uintptr_t)clip_scale | (uintptr_t)wd) & 3) return -1;
+  OptArgs a{w, g, m, v, (bf16*)shadow, (const OptSeg*)segs_dev, (const int4*)table_dev,
+            iterations, OptHyper{kind, lr, mom, b1, b2, eps}, grad_scale, zero_grad, lr_ptr};
+  const ClipArgs k{clip_scale, clip_c, clip_mode};
+  const WdArgs d{wd};
+  if (opt_kind_fused(kind)) optim_apply_wd_kernel<<<nblocks, 256, 0, stream>>>(a, k, d);
+  else optim_apply_ext_wd_kernel<<<nblocks, 256, 0, stream>>>(a, k, d);
   TDE_LAUNCH_CHECK();
   return 0;
 }

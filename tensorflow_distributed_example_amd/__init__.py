@@ -23,7 +23,7 @@ if _os.environ.get("TDE_DEBUG_SYNC", "0") not in ("", "0"):   # before any HIP c
 import torch  # noqa: F401,E402  (first: our HIP library reuses torch's libamdhip64/librccl)
 
 from . import backend  # noqa: F401
-from . import data, losses, metrics, optimizers  # noqa: F401
+from . import data, losses, metrics, optimizers, regularizers  # noqa: F401
 from .data import tfds  # noqa: F401
 from .io import export as _export
 from .models import layers as _layers
@@ -94,6 +94,7 @@ keras = _Namespace(
     layers=_layers,
     losses=losses,
     optimizers=optimizers,
+    regularizers=regularizers,
     metrics=metrics,
     backend=backend,
     mixed_precision=_MixedPrecision(),

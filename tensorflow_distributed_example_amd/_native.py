@@ -56,6 +56,12 @@ _HIP_PROTOS = {
     "tde_optim_apply": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, p]),
     "tde_optim_apply_clip": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, i32, f32,
                                    p, p]),
+    "tde_optim_apply_wd": (i32, [p, p, p, p, p, p, p, i32, p, i32, f32, f32, f32, f32, f32, f32, i32, p, i32, f32,
+                                 p, p, p]),
+    "tde_reg_table_size": (i32, [p, p, i32]),
+    "tde_reg_build_table": (i32, [p, p, i32, p]),
+    "tde_reg_grad": (i32, [p, p, p, p, p, i32, p, p]),
+    "tde_reg_finish": (i32, [p, i32, p, p, i32, p]),
     "tde_clip_table_size": (i32, [p, i32]),
     "tde_clip_build_table": (i32, [p, i32, p, p]),
     "tde_clip_sumsq": (i32, [p, p, p, i32, p, p]),

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import backend as K
+from .. import regularizers
 from . import initializers
 
 
@@ -37,10 +38,18 @@ class WeightSpec:
     trainable: bool = True
     aggregation: str = "none"   # SyncOnRead aggregation for non-trainables ("mean")
     layer: "Layer" = field(default=None, repr=False)
+    l1: float = 0.0      # regularizer coefficients (regularizers.py); both zero: none
+    l2: float = 0.0
 
     @property
     def full_name(self):
         return f"{self.layer.name}/{self.name}"
+
+
+def _reg_config(layer, *names):
+    """The regularizers a layer has, serialized (``regularizers.get`` takes the form back); none: no key, so
+    the config of an unregularized layer is what it always was."""
+    return {n: regularizers.serialize(getattr(layer, n)) for n in names if getattr(layer, n) is not None}
 
 
 def _tuple2(v):
@@ -105,6 +114,11 @@ class Layer:
 
     def __init__(self, name: Optional[str] = None, input_shape=None, trainable=True, **kwargs):
         for k in kwargs:
+            if k == "activity_regularizer":
+                if kwargs[k] is None:
+                    continue
+                raise TypeError(f"{type(self).__name__}: activity_regularizer is not supported (weight regularizers "
+                                "are: kernel_regularizer / bias_regularizer, gamma_regularizer / beta_regularizer)")
             if k not in ("dtype", "batch_input_shape", "input_dim"):
                 raise TypeError(f"{type(self).__name__}: unexpected argument {k!r}")
         if "input_dim" in kwargs and input_shape is None:
@@ -119,9 +133,11 @@ class Layer:
         self._model = None  # owning model (weights live in its ParamStore)
 
     # ---- building
-    def add_weight(self, name, shape, initializer="zeros", trainable=True, aggregation="none"):
+    def add_weight(self, name, shape, initializer="zeros", trainable=True, aggregation="none", regularizer=None):
+        reg = regularizers.get(regularizer)
+        l1, l2 = reg.coefficients if reg is not None else (0.0, 0.0)
         spec = WeightSpec(name, tuple(int(s) for s in shape), initializers.get(initializer),
-                          trainable and self.trainable, aggregation, self)
+                          trainable and self.trainable, aggregation, self, l1, l2)
         self.weight_specs.append(spec)
         return spec
 
@@ -193,8 +209,10 @@ class Conv2D(Layer):
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", activation=None,
                  use_bias=True, kernel_initializer="glorot_uniform", bias_initializer="zeros",
-                 data_format=None, dilation_rate=(1, 1), **kw):
+                 data_format=None, dilation_rate=(1, 1), kernel_regularizer=None, bias_regularizer=None, **kw):
         super().__init__(**kw)
+        self.kernel_regularizer = regularizers.get(kernel_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
         if data_format not in (None, "channels_last"):
             raise ValueError("only channels_last is supported (Keras default)")
         if _tuple2(dilation_rate) != (1, 1):
@@ -213,9 +231,10 @@ class Conv2D(Layer):
     def build(self, input_shape):
         cin = input_shape[-1]
         kh, kw = self.kernel_size
-        self.add_weight("kernel", (kh, kw, cin, self.filters), self.kernel_initializer)
+        self.add_weight("kernel", (kh, kw, cin, self.filters), self.kernel_initializer,
+                        regularizer=self.kernel_regularizer)
         if self.use_bias:
-            self.add_weight("bias", (self.filters,), self.bias_initializer)
+            self.add_weight("bias", (self.filters,), self.bias_initializer, regularizer=self.bias_regularizer)
         self.built = True
 
     def pads(self, input_shape):
@@ -245,15 +264,18 @@ class Conv2D(Layer):
 
     def get_config(self):
         return dict(name=self.name, filters=self.filters, kernel_size=self.kernel_size, strides=self.strides,
-                    padding=self.padding, activation=self.activation, use_bias=self.use_bias)
+                    padding=self.padding, activation=self.activation, use_bias=self.use_bias,
+                    **_reg_config(self, "kernel_regularizer", "bias_regularizer"))
 
 
 class Dense(Layer):
     _prefix = "dense"
 
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer="glorot_uniform",
-                 bias_initializer="zeros", **kw):
+                 bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None, **kw):
         super().__init__(**kw)
+        self.kernel_regularizer = regularizers.get(kernel_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
         self.units = int(units)
         self.activation = get_activation(activation)
         self.use_bias = use_bias
@@ -261,9 +283,10 @@ class Dense(Layer):
         self.bias_initializer = bias_initializer
 
     def build(self, input_shape):
-        self.add_weight("kernel", (input_shape[-1], self.units), self.kernel_initializer)
+        self.add_weight("kernel", (input_shape[-1], self.units), self.kernel_initializer,
+                        regularizer=self.kernel_regularizer)
         if self.use_bias:
-            self.add_weight("bias", (self.units,), self.bias_initializer)
+            self.add_weight("bias", (self.units,), self.bias_initializer, regularizer=self.bias_regularizer)
         self.built = True
 
     def compute_output_shape(self, s):
@@ -276,7 +299,8 @@ class Dense(Layer):
         return apply_activation(y, self.activation)
 
     def get_config(self):
-        return dict(name=self.name, units=self.units, activation=self.activation, use_bias=self.use_bias)
+        return dict(name=self.name, units=self.units, activation=self.activation, use_bias=self.use_bias,
+                    **_reg_config(self, "kernel_regularizer", "bias_regularizer"))
 
 
 class _Pooling2D(Layer):
@@ -438,8 +462,11 @@ class BatchNormalization(Layer):
 
     def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True,
                  beta_initializer="zeros", gamma_initializer="ones",
-                 moving_mean_initializer="zeros", moving_variance_initializer="ones", **kw):
+                 moving_mean_initializer="zeros", moving_variance_initializer="ones", beta_regularizer=None,
+                 gamma_regularizer=None, **kw):
         super().__init__(**kw)
+        self.beta_regularizer = regularizers.get(beta_regularizer)
+        self.gamma_regularizer = regularizers.get(gamma_regularizer)
         if axis not in (-1,):
             raise ValueError("BatchNormalization: only axis=-1 (channels_last) is supported")
         self.momentum = float(momentum)
@@ -451,9 +478,9 @@ class BatchNormalization(Layer):
     def build(self, input_shape):
         c = input_shape[-1]
         if self.scale:
-            self.add_weight("gamma", (c,), self.inits[1])
+            self.add_weight("gamma", (c,), self.inits[1], regularizer=self.gamma_regularizer)
         if self.center:
-            self.add_weight("beta", (c,), self.inits[0])
+            self.add_weight("beta", (c,), self.inits[0], regularizer=self.beta_regularizer)
         self.add_weight("moving_mean", (c,), self.inits[2], trainable=False, aggregation="mean")
         self.add_weight("moving_variance", (c,), self.inits[3], trainable=False, aggregation="mean")
         self.built = True
@@ -488,7 +515,7 @@ class BatchNormalization(Layer):
 
     def get_config(self):
         return dict(name=self.name, momentum=self.momentum, epsilon=self.epsilon, center=self.center,
-                    scale=self.scale)
+                    scale=self.scale, **_reg_config(self, "beta_regularizer", "gamma_regularizer"))
 
 
 class Add(Layer):

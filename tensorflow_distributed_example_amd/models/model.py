@@ -154,6 +154,19 @@ class Model:
     def variable_names(self):
         return [s.full_name for s in self._spec_list()]
 
+    @property
+    def losses(self):
+        """The regularization penalties of the current weights, one host float64 scalar per regularized
+        variable (``l1 * sum|w| + l2 * sum w^2``), in variable order; ``fit`` and ``evaluate`` report the mean
+        per-sample loss plus their sum."""
+        self._require_built()
+        out = []
+        for s in self._spec_list():
+            if s.trainable and (s.l1 or s.l2):
+                w = self._store.view(s.full_name).detach().double().cpu()
+                out.append(s.l1 * w.abs().sum() + s.l2 * w.square().sum())
+        return out
+
     def get_weights(self):
         self._require_built()
         state = self._sync_on_read()

@@ -97,17 +97,24 @@ def mnist_mlp(name=None):
     ], name=name)
 
 
-def _basic_block(x, filters, stride, name):
+def _l2(l2):
+    """kernel_regularizer of the ResNets' conv and dense kernels: ``l2=None`` builds the unregularized model."""
+    from .. import regularizers
+    return None if l2 is None else regularizers.L2(l2)
+
+
+def _basic_block(x, filters, stride, name, l2=None):
     """ResNet v1 BasicBlock: 3x3(s) - BN - ReLU - 3x3 - BN, + (projection) shortcut, ReLU."""
     y = L.Conv2D(filters, 3, strides=stride, padding="same", use_bias=False, kernel_initializer="he_normal",
-                 name=f"{name}_conv1")(x)
+                 kernel_regularizer=_l2(l2), name=f"{name}_conv1")(x)
     y = L.BatchNormalization(epsilon=1e-5, momentum=0.9, name=f"{name}_bn1")(y)
     y = L.Activation("relu", name=f"{name}_relu1")(y)
-    y = L.Conv2D(filters, 3, padding="same", use_bias=False, kernel_initializer="he_normal", name=f"{name}_conv2")(y)
+    y = L.Conv2D(filters, 3, padding="same", use_bias=False, kernel_initializer="he_normal",
+                 kernel_regularizer=_l2(l2), name=f"{name}_conv2")(y)
     y = L.BatchNormalization(epsilon=1e-5, momentum=0.9, name=f"{name}_bn2")(y)
     if stride != 1 or x.shape[-1] != filters:
         s = L.Conv2D(filters, 1, strides=stride, use_bias=False, kernel_initializer="he_normal",
-                     name=f"{name}_proj")(x)
+                     kernel_regularizer=_l2(l2), name=f"{name}_proj")(x)
         s = L.BatchNormalization(epsilon=1e-5, momentum=0.9, name=f"{name}_proj_bn")(s)
     else:
         s = x
@@ -116,32 +123,33 @@ def _basic_block(x, filters, stride, name):
 
 
 def resnet(stage_blocks=(2, 2, 2, 2), filters=(64, 128, 256, 512), input_shape=(224, 224, 3), classes=1000,
-           stem_filters=None, name="resnet"):
+           stem_filters=None, name="resnet", l2=None):
     """BasicBlock ResNet v1 (functional API, TF-'SAME' padding: asymmetric (2,3) for the 7x7/2 stem at
     224): 7x7/2 conv-BN-ReLU stem, 3x3/2 max-pool, stages of BasicBlocks (first block of stages 2+
-    strides 2 with a 1x1 projection shortcut), global average pool, Dense logits."""
+    strides 2 with a 1x1 projection shortcut), global average pool, Dense logits.  ``l2``: the coefficient of
+    an L2 ``kernel_regularizer`` on every conv and dense kernel (the usual 1e-4 / 5e-4 of ResNet training)."""
     from .model import Model
     inp = L.Input(input_shape)
     x = L.Conv2D(stem_filters or filters[0], 7, strides=2, padding="same", use_bias=False,
-                 kernel_initializer="he_normal", name="conv1")(inp)
+                 kernel_initializer="he_normal", kernel_regularizer=_l2(l2), name="conv1")(inp)
     x = L.BatchNormalization(epsilon=1e-5, momentum=0.9, name="conv1_bn")(x)
     x = L.Activation("relu", name="conv1_relu")(x)
     x = L.MaxPooling2D(3, strides=2, padding="same", name="pool1")(x)
     for i, (nb, f) in enumerate(zip(stage_blocks, filters)):
         for j in range(nb):
-            x = _basic_block(x, f, 2 if (i > 0 and j == 0) else 1, f"stage{i + 1}_block{j + 1}")
+            x = _basic_block(x, f, 2 if (i > 0 and j == 0) else 1, f"stage{i + 1}_block{j + 1}", l2)
     x = L.GlobalAveragePooling2D(name="avg_pool")(x)
-    out = L.Dense(classes, name="fc")(x)
+    out = L.Dense(classes, kernel_regularizer=_l2(l2), name="fc")(x)
     return Model(inputs=inp, outputs=out, name=name)
 
 
-def resnet18(input_shape=(224, 224, 3), classes=1000, name="resnet18"):
+def resnet18(input_shape=(224, 224, 3), classes=1000, name="resnet18", l2=None):
     """ResNet-18 (BASELINE.json stress config; not in the reference): 11.69M parameters at 224/1000."""
-    return resnet((2, 2, 2, 2), (64, 128, 256, 512), input_shape, classes, name=name)
+    return resnet((2, 2, 2, 2), (64, 128, 256, 512), input_shape, classes, name=name, l2=l2)
 
 
-def mini_resnet(input_shape=(32, 32, 3), classes=10, name="mini_resnet"):
+def mini_resnet(input_shape=(32, 32, 3), classes=10, name="mini_resnet", l2=None):
     """A two-stage BasicBlock ResNet (16 / 32 filters) on 32x32x3: ResNet-18's layer kinds (stem conv, BN,
     max-pool, projection shortcut, residual add, GAP, Dense) at test size."""
-    return resnet((1, 1), (16, 32), input_shape, classes, name=name)
+    return resnet((1, 1), (16, 32), input_shape, classes, name=name, l2=l2)
 

@@ -17,6 +17,13 @@ inside the captured step (csrc/include/tde_sched.h), so ``key()`` holds its conf
 before the update (TF 2.4+ order: after the all-reduce): ``clip_reference`` is the torch form, on the GPU two
 norm launches and a clipped variant of the multi-tensor launch run inside the captured step
 (csrc/include/tde_clip.h).
+
+``weight_decay`` (Keras 2.11+; ``AdamW``) is decoupled weight decay: before the gradient step of a variable,
+``w <- w - (w * weight_decay) * lr`` with the rate this step uses (the schedule's value, never Adam's
+bias-corrected step size); the step then starts from the decayed weight.  Every trainable variable decays unless
+``exclude_from_weight_decay`` names it; ``0`` and ``None`` mean off.  ``decay_reference`` is the torch form, on
+the GPU the WD variants of the multi-tensor launch read a per-variable decay (csrc/include/tde_reg.h).  The
+layers' weight regularizers (``regularizers.py``) are applied to the aggregated gradient before a clip.
 """
 from __future__ import annotations
 
@@ -53,10 +60,23 @@ def _clip_of(clipnorm, clipvalue, global_clipnorm):
     return mode, c
 
 
+def _decay_of(weight_decay):
+    if weight_decay is None:
+        return None
+    try:
+        wd = float(weight_decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"weight_decay must be a finite float >= 0 (got {weight_decay!r})") from None
+    if not (wd >= 0.0 and math.isfinite(wd)):
+        raise ValueError(f"weight_decay must be a finite float >= 0 (got {weight_decay!r})")
+    return wd
+
+
 class Optimizer:
     kind = "sgd"
 
-    def __init__(self, learning_rate=0.01, name=None, clipnorm=None, clipvalue=None, global_clipnorm=None, **kw):
+    def __init__(self, learning_rate=0.01, name=None, clipnorm=None, clipvalue=None, global_clipnorm=None,
+                 weight_decay=None, **kw):
         if "lr" in kw:   # the Keras 2 spelling
             learning_rate = kw.pop("lr")
         if kw:
@@ -66,6 +86,47 @@ class Optimizer:
         self.name = name or type(self).__name__
         self.iterations = 0  # host mirror; device counter lives in the program
         self._clip = _clip_of(clipnorm, clipvalue, global_clipnorm)
+        self.weight_decay = _decay_of(weight_decay)
+        self._wd_exclude = (frozenset(), ())   # (full names, substrings of full names)
+        self._plan_built = False               # a plan holds the per-variable decay: exclusions are closed
+
+    @property
+    def decay(self):
+        """The decoupled weight decay in effect: a positive float, or None (``weight_decay`` None or 0)."""
+        return self.weight_decay if self.weight_decay else None
+
+    def exclude_from_weight_decay(self, var_list=None, var_names=None):
+        """Keras's: the variables of ``var_list`` (full names, or objects with a ``full_name``) and every
+        variable whose full name contains one of ``var_names`` do not decay.  Before the first plan is built."""
+        if self._plan_built:
+            raise ValueError("exclude_from_weight_decay() must be called before the optimizer has built a plan "
+                             "(before fit / the first training step)")
+        names = set(self._wd_exclude[0])
+        for v in var_list or []:
+            n = v if isinstance(v, str) else getattr(v, "full_name", None)
+            if not isinstance(n, str):
+                raise TypeError(f"exclude_from_weight_decay: {v!r} is neither a variable name nor has a full_name")
+            names.add(n)
+        subs = tuple(self._wd_exclude[1]) + tuple(str(n) for n in (var_names or []))
+        self._wd_exclude = (frozenset(names), subs)
+
+    def decays(self, full_name):
+        """Whether the variable ``full_name`` decays under this optimizer."""
+        if self.decay is None or full_name in self._wd_exclude[0]:
+            return False
+        return not any(sub in full_name for sub in self._wd_exclude[1])
+
+    @torch.no_grad()
+    def decay_reference(self, w, segments, step):
+        """Decoupled weight decay of the flat weights ``w`` in place, the kernels' order of operations:
+        ``w - (w * wd) * lr`` over ``segments``, the (offset, numel) of the variables that decay."""
+        if self.decay is None:
+            return w
+        lr = self.lr_at(step)
+        for o, n in segments:
+            x = w[o: o + n]
+            x.sub_((x * self.decay) * lr)
+        return w
 
     @property
     def clip(self):
@@ -149,7 +210,7 @@ class Optimizer:
         sch = self.schedule
         # a schedule's key is its configuration: constant over the run, so nothing is captured again
         return (self.kind_id, sch.key() if sch is not None else self._lr, tuple(sorted(self.hparams().items())),
-                self._clip)
+                self._clip, self.decay, (tuple(sorted(self._wd_exclude[0])), self._wd_exclude[1]))
 
     def apply_reference(self, w, g, slots, step):
         raise NotImplementedError
@@ -159,6 +220,8 @@ class Optimizer:
         cfg = {"name": self.name, "learning_rate": schedules.serialize(sch) if sch is not None else self._lr}
         if self._clip is not None:   # the one that is set: ``type(opt)(**config)`` rebuilds the optimizer
             cfg[self._clip[0]] = self._clip[1]
+        if self.weight_decay is not None:   # like the clip: only when given, so an optimizer without it keeps its config
+            cfg["weight_decay"] = self.weight_decay
         return cfg
 
 
@@ -205,6 +268,11 @@ class GradientDescentOptimizer(SGD):
     def __init__(self, learning_rate, use_locking=False, name="GradientDescent"):
         super().__init__(learning_rate, 0.0, False, name)
 
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.pop("weight_decay", None)   # not an argument of the TF1 optimizer
+        return cfg
+
 
 class Adam(Optimizer):
     kind = "adam"
@@ -230,6 +298,16 @@ class Adam(Optimizer):
 
     def get_config(self):
         return {**super().get_config(), "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
+
+
+class AdamW(Adam):
+    """Keras ``AdamW``: Adam with decoupled weight decay (Loshchilov & Hutter), Keras's defaults."""
+
+    def __init__(self, learning_rate=0.001, weight_decay=0.004, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="AdamW",
+                 **kw):
+        if weight_decay is None:
+            raise ValueError("AdamW needs a weight_decay (got None); Adam is the optimizer without one")
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, name, weight_decay=weight_decay, **kw)
 
 
 class RMSprop(Optimizer):
@@ -285,6 +363,8 @@ def get(identifier):
             return SGD()
         if k == "adam":
             return Adam()
+        if k == "adamw":
+            return AdamW()
         if k == "rmsprop":
             return RMSprop()
     raise ValueError(f"unsupported optimizer {identifier!r}")

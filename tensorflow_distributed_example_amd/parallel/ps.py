@@ -201,11 +201,19 @@ class PSClient:
                 gstep, ticket = so.value, to.value
         return gstep, ticket
 
-    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7, learning_rate=None, clip=None):
+    def set_optimizer(self, kind, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-7, learning_rate=None, clip=None,
+                      weight_decay=None, regularizers=None):
         """The update every ps task applies on a push: 0 SGD, 1 momentum, 2 Nesterov, 3 Adam (Keras forms).
         ``learning_rate`` (optional) is only checked: the rate itself travels with every push.  ``clip``
         (optional, ``optimizer.clip``) is only checked too: the ps tasks apply each push as it arrives."""
         from ..schedules import LearningRateSchedule
+        if weight_decay:   # (optional, ``optimizer.decay``) only checked, like ``clip``
+            raise ValueError(f"the parameter server applies the plain update (got weight_decay={weight_decay!r}; "
+                             "weight_decay is not supported under ParameterServerStrategy)")
+        if regularizers:   # (optional, ``regularizers.coefficients(model)``) only checked
+            raise ValueError("the parameter server applies each pushed gradient as it arrives (got weight "
+                             f"regularizers on {', '.join(sorted(regularizers))}; kernel_regularizer / bias_regularizer "
+                             "/ gamma_regularizer / beta_regularizer are not supported under ParameterServerStrategy)")
         if clip is not None:
             raise ValueError(f"the parameter server applies unclipped gradients (got {clip[0]}={clip[1]!r}; "
                              "clipnorm, clipvalue and global_clipnorm are not supported under "

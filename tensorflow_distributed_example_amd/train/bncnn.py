@@ -236,7 +236,7 @@ class BnCnnPlan(ReplicaPlan):
         self.keep = torch.zeros(nrt * (self.Dp // 16) * 64, dtype=torch.int32, device=self.device)
         H0, W0, C0 = self.blocks[0]["geo"].H, self.blocks[0]["geo"].W, self.blocks[0]["geo"].C
         self.x_stride = H0 * W0 * C0
-        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
+        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations, self) if optimizer is not None else None
         self._bn_segs = self._bn_gradient_segments()
 
     def head_fold_ok(self, B):
@@ -337,6 +337,7 @@ class BnCnnPlan(ReplicaPlan):
 
     def train_step(self, x, y, B=None):
         B = self.B if B is None else B
+        self.step_rows = B
         self._check_input(x, B)
         lib, s = self.lib, N.stream_ptr()
         fold = self.head_fold_ok(B)

@@ -272,6 +272,20 @@ class Estimator:
                 raise ValueError(f"ParameterServerStrategy does not support {opt.clip[0]}={opt.clip[1]!r} of "
                                  f"{opt.name}: the parameter server applies unclipped gradients (clipnorm, "
                                  "clipvalue and global_clipnorm need a synchronous strategy)")
+            if opt is not None and opt.decay is not None:
+                raise ValueError(f"ParameterServerStrategy does not support weight_decay={opt.weight_decay!r} of "
+                                 f"{opt.name}: the parameter server applies the plain update (decoupled weight "
+                                 "decay needs a synchronous strategy)")
+            from .. import regularizers as RG
+            reg = RG.coefficients(self.model) if self.model is not None else {}
+            if reg:
+                # the penalty's gradient is added to the aggregated gradient: the ps tasks see single pushes
+                name = next(iter(reg))
+                layer, short = name.rsplit("/", 1)
+                raise ValueError(f"ParameterServerStrategy does not support weight regularizers (the "
+                                 f"{short}_regularizer of {layer}: l1={reg[name][0]!r}, l2={reg[name][1]!r}): "
+                                 "kernel_regularizer / bias_regularizer / gamma_regularizer / beta_regularizer "
+                                 "need a synchronous strategy")
             return self._train_ps(st, input_fn, hooks, steps, max_steps, saving_listeners)
         return self._train_sync(st, input_fn, hooks, steps, max_steps, saving_listeners)
 
@@ -389,9 +403,11 @@ class Estimator:
             shapes = {n: tuple(m._store.segments[n].shape) for n in m._store.order}
             self._psc = strategy.client(shapes)
             hp = m.optimizer.hparams()
+            from .. import regularizers as RG
             self._psc.set_optimizer(m.optimizer.kind_id, momentum=hp["mom"], beta1=hp["b1"], beta2=hp["b2"],
                                     epsilon=hp["eps"], learning_rate=m.optimizer.learning_rate,
-                                    clip=m.optimizer.clip)
+                                    clip=m.optimizer.clip, weight_decay=m.optimizer.decay,
+                                    regularizers=RG.coefficients(m))
         return self._psc
 
     def _train_ps(self, strategy, input_fn, hooks, steps, max_steps, saving_listeners):

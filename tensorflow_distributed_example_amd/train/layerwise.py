@@ -149,7 +149,7 @@ class LayerwisePlan(PG.ReplicaPlan):
                 shadows[name] = want
         self.shadows = shadows
         if optimizer is not None:
-            self.opt = PG.OptimizerKernel(store, optimizer, shadows, self.iterations)
+            self.opt = PG.OptimizerKernel(store, optimizer, shadows, self.iterations, self)
             self._sh = self.opt
         else:
             from ..optimizers import SGD
@@ -381,6 +381,7 @@ class LayerwisePlan(PG.ReplicaPlan):
         order) has been enqueued — the hook the Program uses to start gradient-bucket all-reduces
         while the rest of the backward is still running (see ``grad_buckets``)."""
         B = self.B if B is None else B
+        self.step_rows = B
         self._input(x, B)
         self._labels = y
         for st in self.stages:

@@ -59,6 +59,16 @@ class ReplicaPlan:
         self._pushed = False
         self._opt_key_set = None   # optimizer.key() the descriptors of the current step mode were built at
         self._zl = None
+        # weight regularizers (regularizers.py): [(offset, numel, l1, l2)] of the regularized variables
+        from .. import regularizers as RG
+        self.reg_segs = RG.segments(model, store)
+        # rows of the running step (train_step sets it): the regularizers' penalty enters the loss sum once
+        # per row, as the per-sample losses do
+        self.step_rows = self.B
+        self._reg_eval = None      # eval programs: the penalty launches (GPU), made on first use
+        self._reg_stale = True     # the penalty partials are older than the weights
+        if optimizer is not None:
+            optimizer._plan_built = True   # the per-variable decay is settled: exclude_from_weight_decay raises
 
     def reset_metrics(self):
         self.metrics.zero_()
@@ -105,8 +115,29 @@ class ReplicaPlan:
         # multi-tensor launch reads it from the device word the schedule launch wrote (OptimizerKernel)
         # gradient clipping too: a norm needs every gradient before any update, a grid-wide dependency the
         # fused steps do not have; the norm launches run in front of the multi-tensor launch
+        # weight regularizers and decoupled weight decay as well: the penalty's gradient is added to the
+        # aggregated gradient in front of the clip, and the decay is a variant of the multi-tensor launch alone
         return (self.optimizer is not None and self.optimizer.kind_id in FUSED_KINDS
-                and self.optimizer.schedule is None and self.optimizer.clip is None)
+                and self.optimizer.schedule is None and self.optimizer.clip is None
+                and not self.reg_segs and self.optimizer.decay is None)
+
+    def decay_segments(self):
+        """(offset, numel) of the trainable variables the optimizer's weight decay applies to."""
+        st, opt = self.store, self.optimizer
+        return [(st.segments[n].offset, st.segments[n].numel) for n in st.names(trainable=True) if opt.decays(n)]
+
+    def add_eval_penalty(self, rows):
+        """After an ``eval_step`` of ``rows`` rows: metrics[0] += rows * (the regularizers' penalty of the
+        weights).  The partials are computed once per evaluation (``_reg_stale``: the Program marks them when
+        the weights may have changed), the finish launch runs per batch."""
+        if not self.reg_segs or rows <= 0:
+            return
+        if self._reg_eval is None:
+            self._reg_eval = WeightRegKernel(self.store, self.reg_segs)
+        if self._reg_stale:
+            self._reg_eval.grad(None)
+            self._reg_stale = False
+        self._reg_eval.finish(self.metrics, rows)
 
     def set_step_mode(self, mode):
         if not self.supports_step_mode(mode):
@@ -164,6 +195,8 @@ class ReplicaPlan:
         """Before an execution is launched or captured: pick up optimizer hyper-parameter changes."""
         if self.step_mode in self.hyper_by_value and self._opt_key_set != self._opt_key():
             self.set_step_mode(self.step_mode)
+        if getattr(self, "opt", None) is not None:
+            self.opt.refresh()
 
 
 # ---------------------------------------------------------------------------------------
@@ -216,6 +249,7 @@ class ReferencePlan(ReplicaPlan):
 
     def train_step(self, x, y, B=None):
         B = x.shape[0] if B is None else B
+        self.step_rows = B
         x, y = x[:B], y[:B]
         wl = self.store.w.detach().requires_grad_(True)
         W = self._weights(wl)
@@ -232,17 +266,30 @@ class ReferencePlan(ReplicaPlan):
     def _acc(self, out, y, ls):
         yy = torch.as_tensor(y, device=out.device).reshape(-1).long()
         correct = (out.argmax(dim=1) == yy).sum().float()
-        self.metrics += torch.stack([ls.sum().float(), correct, torch.tensor(float(ls.shape[0]), device=out.device),
+        loss_sum = ls.sum().float()
+        if self.reg_segs:   # the penalty of the weights this forward used, once per row
+            from .. import regularizers as RG
+            loss_sum = loss_sum + float(ls.shape[0]) * RG.penalty(self.store.w.detach(), self.reg_segs).float()
+        self.metrics += torch.stack([loss_sum, correct, torch.tensor(float(ls.shape[0]), device=out.device),
                                      torch.zeros((), device=out.device)])
+
+    def add_eval_penalty(self, rows):
+        """``_acc`` has added it already."""
 
     @torch.no_grad()
     def apply(self):
         st = self.store
         slots = {n: st.slot(n) for n in self.optimizer.slot_names()}
+        step = int(self.iterations.item())
+        if self.reg_segs:   # on the aggregated gradient, in front of the clip: Keras clips the total loss's gradient
+            from .. import regularizers as RG
+            RG.reg_reference(st.w, st.g, self.reg_segs)
         if self.optimizer.clip is not None:   # st.g is the aggregated gradient by now: clipped after the all-reduce
             segs = [(st.segments[n].offset, st.segments[n].numel) for n in st.names(trainable=True)]
             self.optimizer.clip_reference(st.g, segs)
-        self.optimizer.apply_reference(st.w, st.g, slots, int(self.iterations.item()))
+        if self.optimizer.decay is not None:   # the step starts from the decayed weight
+            self.optimizer.decay_reference(st.w, self.decay_segments(), step)
+        self.optimizer.apply_reference(st.w, st.g, slots, step)
         st.g.zero_()
         self.iterations += 1
 
@@ -263,6 +310,48 @@ class ReferencePlan(ReplicaPlan):
 
 
 # ---------------------------------------------------------------------------------------
+_OPTSEG = np.dtype([("off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("sh", "<i8"), ("sht", "<i8")])
+
+
+class WeightRegKernel:
+    """Device-side state of the weight-regularizer launches of one replica (csrc/include/tde_reg.h,
+    csrc/kernels/weightreg.hip): the table over the regularized segments, the penalty partials and the penalty
+    word.  ``grad(g)`` adds the penalty's gradient to ``g`` (None: partials only) and ``finish(metrics, rows)``
+    sums the partials into ``penalty`` and adds ``rows * penalty`` to ``metrics[0]``; both on the current stream."""
+
+    def __init__(self, store, reg_segs):
+        from .. import _native as N
+        self.N = N
+        self.store = store
+        segs = np.array([(o, 1, n, -1, -1) for o, n, _, _ in reg_segs], dtype=_OPTSEG)
+        coef = np.ascontiguousarray(np.array([(c1, c2) for _, _, c1, c2 in reg_segs], dtype=np.float32).reshape(-1, 2))
+        lib = N.hip()
+        ne = lib.tde_reg_table_size(segs.ctypes.data, coef.ctypes.data, len(segs))
+        N.check(min(ne, 0), "tde_reg_table_size")
+        ents = np.zeros((max(ne, 1), 2), dtype=np.int32)
+        N.check(min(lib.tde_reg_build_table(segs.ctypes.data, coef.ctypes.data, len(segs), ents.ctypes.data), 0),
+                "tde_reg_build_table")
+        dev = store.device
+        self.nent = ne
+        self.segs_dev = torch.from_numpy(segs.view(np.uint8).copy()).to(dev)
+        self.coef_dev = torch.from_numpy(coef).to(dev)
+        self.ents_dev = torch.from_numpy(ents).to(dev)
+        self.partials = torch.zeros(max(ne, 1), dtype=torch.float32, device=dev)
+        self.penalty = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def grad(self, g):
+        N = self.N
+        rc = N.hip().tde_reg_grad(self.store.w.data_ptr(), N.ptr(g), self.segs_dev.data_ptr(), self.coef_dev.data_ptr(),
+                                  self.ents_dev.data_ptr(), self.nent, self.partials.data_ptr(), N.stream_ptr())
+        N.check(rc, "tde_reg_grad")
+
+    def finish(self, metrics, rows):
+        N = self.N
+        rc = N.hip().tde_reg_finish(self.partials.data_ptr(), self.nent, self.penalty.data_ptr(), N.ptr(metrics),
+                                    int(rows), N.stream_ptr())
+        N.check(rc, "tde_reg_finish")
+
+
 class OptimizerKernel:
     """Device-side state for the multi-tensor optimizer kernel of one replica.  Under a learning-rate schedule
     it owns the device word ``lr_word``: ``apply()`` first launches the schedule at ``iterations + sched_bias``
@@ -272,9 +361,12 @@ class OptimizerKernel:
     # iterations - 1 (csrc/include/tde_sched.h)
     sched_bias = -1
 
-    def __init__(self, store: P.ParamStore, optimizer, shadows: dict, iterations):
+    def __init__(self, store: P.ParamStore, optimizer, shadows: dict, iterations, plan=None):
         from .. import _native as N
         self.N = N
+        # the plan this kernel updates for: its regularized segments, its metrics (the penalty joins the loss
+        # sum there) and the rows of its running step
+        self.plan = plan
         self.store = store
         self.optimizer = optimizer
         self.iterations = iterations
@@ -304,8 +396,7 @@ class OptimizerKernel:
                 self.shadow_views[(name, "row")] = self.shadow[sh: sh + rows * cols].view(rows, cols)
             if sht >= 0:
                 self.shadow_views[(name, "col")] = self.shadow[sht: sht + rows * cols].view(cols, rows)
-        dt = np.dtype([("off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("sh", "<i8"), ("sht", "<i8")])
-        arr = np.array(segs, dtype=dt)
+        arr = np.array(segs, dtype=_OPTSEG)
         self._segs_host = arr
         lib = N.hip()
         nb = lib.tde_optim_table_size(arr.ctypes.data, len(arr))
@@ -334,7 +425,27 @@ class OptimizerKernel:
             self.clip_partials = torch.zeros(max(ne, 1), dtype=torch.float32, device=store.device)
             self.clip_norm = torch.zeros(max(nw, 1), dtype=torch.float32, device=store.device)
             self.clip_scale = torch.ones(max(nw, 1), dtype=torch.float32, device=store.device)
+        # weight regularizers and decoupled weight decay (csrc/include/tde_reg.h): the regularizer launches'
+        # state and the per-segment decay, only when the model or the optimizer has them
+        self.reg = WeightRegKernel(store, plan.reg_segs) if plan is not None and plan.reg_segs else None
+        self.wd_dev = self._wd_key = None
+        self.refresh()
         self.refresh_shadows()
+
+    def _decay_key(self):
+        return (self.optimizer.decay, self.optimizer._wd_exclude)
+
+    def refresh(self):
+        """Before an execution is launched or captured: the per-segment decay follows the optimizer."""
+        if self._wd_key == self._decay_key():
+            return
+        opt, names = self.optimizer, self.store.names(trainable=True)
+        self._wd_key = self._decay_key()
+        if opt.decay is None:
+            self.wd_dev = None
+            return
+        wd = np.array([opt.decay if opt.decays(n) else 0.0 for n in names] or [0.0], dtype=np.float32)
+        self.wd_dev = torch.from_numpy(wd).to(self.store.device)
 
     def refresh_shadows(self):
         if not self.shadow_views:   # f32 plans read the master weights: nothing to refresh
@@ -346,7 +457,9 @@ class OptimizerKernel:
                                             N.stream_ptr())
         N.check(rc, "tde_shadow_refresh")
 
-    def apply(self, zero_grad=True):
+    def apply(self, zero_grad=True, rows=None):
+        """schedule -> regularizers (gradient, penalty) -> clip norms -> the (WD / CLIP) apply.  ``rows``: the
+        rows of the step (default: the plan's ``step_rows``), what the step's loss head was given."""
         N = self.N
         st = self.store
         from ..ops.kernels import opt_hyper, opt_slots
@@ -361,9 +474,15 @@ class OptimizerKernel:
                 self._sched, self._sched_key = K.lr_sched(sch), sch.key()
             K.lr_schedule(self._sched, self.iterations, self.sched_bias, self.lr_word)
         lr_ptr = N.ptr(self.lr_word) if sch is not None else None
-        if self.optimizer.clip is not None:
+        if self.reg is not None:
+            self.reg.grad(st.g)
+            self.reg.finish(self.plan.metrics, self.plan.step_rows if rows is None else rows)
+        if self.optimizer.decay is not None and self.wd_dev is None:
+            self.refresh()
+        if self.optimizer.clip is not None or self.optimizer.decay is not None:
             from ..optimizers import CLIP_MODE
-            mode, c = CLIP_MODE[self.optimizer.clip[0]], float(self.optimizer.clip[1])
+            mode, c = (CLIP_MODE[self.optimizer.clip[0]], float(self.optimizer.clip[1])) \
+                if self.optimizer.clip is not None else (0, 0.0)
             lib = N.hip()
             if self.clip_scale is not None:   # a norm mode: partials, then norm and scale, on the step's stream
                 rc = lib.tde_clip_sumsq(st.g.data_ptr(), self.segs_dev.data_ptr(), self.clip_ents_dev.data_ptr(),
@@ -373,6 +492,14 @@ class OptimizerKernel:
                                         len(self._segs_host), self.clip_nent, mode, c, self.clip_norm.data_ptr(),
                                         self.clip_scale.data_ptr(), N.stream_ptr())
                 N.check(rc, "tde_clip_scale")
+            if self.optimizer.decay is not None:
+                rc = lib.tde_optim_apply_wd(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v),
+                                            self.shadow.data_ptr(), self.segs_dev.data_ptr(),
+                                            self.table_dev.data_ptr(), self.nblocks, self.iterations.data_ptr(),
+                                            h.kind, h.lr, h.mom, h.b1, h.b2, h.eps, 1.0, int(zero_grad), lr_ptr, mode,
+                                            c, N.ptr(self.clip_scale), self.wd_dev.data_ptr(), N.stream_ptr())
+                N.check(rc, "tde_optim_apply_wd")
+                return
             rc = lib.tde_optim_apply_clip(st.w.data_ptr(), st.g.data_ptr(), N.ptr(m), N.ptr(v),
                                           self.shadow.data_ptr(), self.segs_dev.data_ptr(),
                                           self.table_dev.data_ptr(), self.nblocks, self.iterations.data_ptr(), h.kind,
@@ -676,7 +803,7 @@ class ConvNetPlan(SmallCnnPlan):
             shadows = {}
         else:
             shadows = {self.names["w1"]: ("row",) if self.w1_rows else ("row", "col")}
-        self.opt = OptimizerKernel(store, optimizer, shadows, self.iterations) if optimizer is not None else None
+        self.opt = OptimizerKernel(store, optimizer, shadows, self.iterations, self) if optimizer is not None else None
         self._shadow_only = None
         if self.opt is None and shadows:
             # eval/predict-only plan still needs the bf16 weight copies
@@ -804,6 +931,7 @@ class ConvNetPlan(SmallCnnPlan):
     def train_step(self, x, y, B=None):
         K = self.K
         B = self.B if B is None else B
+        self.step_rows = B
         q = self.parity
         local = self.step_mode == "local"
         self._forward(x, B, self.hpre2[q], True, self._fopt[q] if local else None, train=True, hrep=self.hrep)
@@ -857,7 +985,7 @@ class ConvNetGenPlan(SmallCnnPlan):
         self.Pt = torch.zeros(self.P * self.C, Bp, dtype=torch.float32, device=dev)
         self.amax = torch.zeros(self.P, self.C // 8, Bp, dtype=torch.int64, device=dev)
         self.W1 = store.view(self.names["w1"])
-        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
+        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations, self) if optimizer is not None else None
         self._copt = self._fly = self._hopt = self._commit = None
 
     def _size_replicas(self, foreign):
@@ -900,6 +1028,7 @@ class ConvNetGenPlan(SmallCnnPlan):
     def train_step(self, x, y, B=None):
         K = self.K
         B = self.B if B is None else B
+        self.step_rows = B
         q = self.parity
         local = self.step_mode == "local"
         # the fused step's Adam t is read by every backward workgroup: the forward advances the counter

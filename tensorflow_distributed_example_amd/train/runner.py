@@ -581,6 +581,8 @@ class Program:
                             n = len(per_replica[r][1])
                             if n > 0:
                                 self.plans[r].train_step(self.x_ring[r][0], self.y_ring[r][0], n)
+                            else:
+                                self.plans[r].step_rows = 0
                         if self.group_buckets:   # the same bucket calls as the captured steps, post-backward
                             plans = [self.plans[r] for r in idx]
                             for _, lo, hi in self.group_buckets:
@@ -598,6 +600,7 @@ class Program:
                     self._overlapped_step(0, n)
                 else:
                     plan = self.plans[0]
+                    plan.step_rows = 0
                     with _ctx(plan.device):
                         for _, lo, hi in self.buckets:
                             self.grad_comm.all_reduce_([plan.store.g[lo:hi]])
@@ -608,7 +611,9 @@ class Program:
                 with _ctx(plan.device):
                     if n > 0:
                         plan.train_step(self.x_ring[r][0], self.y_ring[r][0], n)
-                    elif plan.applies_in_step:
+                    else:
+                        plan.step_rows = 0   # no rows: the regularizers' penalty joins no loss sum
+                    if n == 0 and plan.applies_in_step:
                         continue   # no data, nothing to reduce: the fused step has no update to make
             self._reduce_and_apply()
             self._finish()
@@ -626,6 +631,7 @@ class Program:
                 self.x_stage[r].stage(x, self.x_ring[r][0])
                 self.y_stage[r].stage(y, self.y_ring[r][0])
                 self.plans[r].eval_step(self.x_ring[r][0], self.y_ring[r][0], n)
+                self.plans[r].add_eval_penalty(n)   # weight regularizers: the penalty joins the loss sum
 
     def predict_batch(self, x):
         n = len(x)
@@ -660,6 +666,7 @@ class Program:
 
     def on_weights_loaded(self):
         for p in self.plans:
+            p._reg_stale = True   # the regularizers' penalty is computed again at the next evaluation batch
             with _ctx(p.device):
                 p.on_weights_loaded()
 

@@ -260,7 +260,7 @@ class SmallNetPlan(ReplicaPlan):
         self.part = torch.zeros(B, self.npart, dtype=torch.float32, device=dev)
         self.rec = torch.zeros(B, self.nrec, dtype=torch.float32, device=dev)
         self.probs = torch.zeros(B, self.ncls, dtype=torch.float32, device=dev)
-        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations) if optimizer is not None else None
+        self.opt = OptimizerKernel(store, optimizer, {}, self.iterations, self) if optimizer is not None else None
         # the step index of the dropout masks: steps completed before the running one.  The step kernel
         # increments ``iterations`` while its grid runs, so it reads this word instead, which the weight
         # gradient launch sets to ``iterations`` for the next step.
@@ -275,8 +275,10 @@ class SmallNetPlan(ReplicaPlan):
         if mode == "xgmi":
             return self._opt_fused() and self.device.type == "cuda"
         # A clipping optimizer runs "plain": a norm needs every gradient before any update, and the weight
-        # gradient launch updates each range as its gradient is finished.
+        # gradient launch updates each range as its gradient is finished.  Weight regularizers and decoupled
+        # weight decay too: their launches sit in front of the multi-tensor launch.
         return mode == "plain" or (mode == "local" and self.optimizer is not None and self.optimizer.clip is None
+                                   and not self.reg_segs and self.optimizer.decay is None
                                    and self.device.type == "cuda")
 
     def set_iterations(self, step):
@@ -305,6 +307,7 @@ class SmallNetPlan(ReplicaPlan):
 
     def train_step(self, x, y, B=None):
         B = self.B if B is None else B
+        self.step_rows = B
         self._step(0, x, y, B)
         local = self.step_mode == "local"
         st, opt = self.store, self.optimizer
