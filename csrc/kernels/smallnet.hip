@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "tde_common.h"
+#include "tde_loss.h"
 #include "tde_optim.h"
 #include "tde_philox.h"
 #include "tde_sched.h"
@@ -79,6 +80,12 @@ struct SnArgs {
   long long* stamps;  // optional phase timestamps of workgroup 0 (wall clock, 100 MHz)
   int nonlinear;      // a layer has a tanh / sigmoid code or is an average pool: run sn_step<true>
   int mfma;           // phases (bit 0 fwd, 1 wgrad, 2 dgrad) of the compile-time-geometry convs on the f32 MFMA
+};
+// ... of smallnet_step_loss_kernel: the loss head's spec appended (label smoothing, per-class row weights;
+// tde_loss.h).  A struct and a kernel of their own, as for SnWgradSchedArgs below: smallnet_step_kernel keeps its
+// kernarg layout and its program.
+struct SnLossArgs : SnArgs {
+  LossSpec ls;
 };
 
 // The step kernel holds its per-image program twice (sn_step<NL>, chosen per launch): NL = false knows
@@ -916,8 +923,9 @@ __device__ __forceinline__ void sn_by_cg(int Co, F&& f) {
   else f(std::integral_constant<int, 1>{});
 }
 
-template <bool NL>
-__device__ __forceinline__ void sn_step(const SnArgs& a, float* s) {
+// LOSS (with Args = SnLossArgs): the one-wave loss block follows a.ls; everything else is the same program.
+template <bool NL, bool LOSS = false, class Args = SnArgs>
+__device__ __forceinline__ void sn_step(const Args& a, float* s) {
   const int b = blockIdx.x;
   const bool train = a.mode == 0;
   float* scratch = s;  // [kSnScratch] dense slice partials
@@ -995,19 +1003,34 @@ __device__ __forceinline__ void sn_step(const SnArgs& a, float* s) {
         am = oi;
       }
     }
-    float se = 0.f;
-    for (int c = lane; c < C; c += 64) se += __expf(lg[c] - mx);
+    float se = 0.f, sl = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      se += __expf(lg[c] - mx);
+      if constexpr (LOSS) sl += lg[c];
+    }
     se = wave_sum(se);
     const int y = a.y ? a.y[b] : 0;
     const float ly = (y >= 0 && y < C) ? lg[y] : mx;
-    const float loss = mx + __logf(se) - ly;
+    float loss, w = 1.f;
+    if constexpr (LOSS) {
+      sl = wave_sum(sl);
+      w = loss_row_weight(a.ls, y, C);
+      const float lse = mx + __logf(se);
+      loss = loss_row(a.ls, w, lse, lse - ly, sl, C);   // the weighted loss goes through rec[nrec - 2]
+    } else {
+      loss = mx + __logf(se) - ly;
+    }
     const float corr = am == y ? 1.f : 0.f;
     const float inv = 1.f / se;
     // every lane has read lg[y] above before any lane overwrites the logits below
     __builtin_amdgcn_wave_barrier();
     for (int c = lane; c < C; c += 64) {
       const float p = __expf(lg[c] - mx) * inv;
-      if (train) lg[c] = (p - (c == y ? 1.f : 0.f)) * a.scale;
+      if constexpr (LOSS) {
+        if (train) lg[c] = loss_dlogit(w, p, loss_target(a.ls, c == y, C), a.scale);
+      } else {
+        if (train) lg[c] = (p - (c == y ? 1.f : 0.f)) * a.scale;
+      }
       if (a.mode == 2 && a.probs) a.probs[(long long)b * C + c] = a.probs_softmax ? p : lg[c];
     }
     if (lane == 0) {
@@ -1054,6 +1077,12 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
   __shared__ __attribute__((aligned(16))) float s[kSnLds];
   if (a.nonlinear) sn_step<true>(a, s);
   else sn_step<false>(a, s);
+}
+
+__global__ __launch_bounds__(kSnThreads) void smallnet_step_loss_kernel(SnLossArgs a) {
+  __shared__ __attribute__((aligned(16))) float s[kSnLds];
+  if (a.nonlinear) sn_step<true, true>(a, s);
+  else sn_step<false, true>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1240,13 +1269,12 @@ TDE_API int tde_smallnet_limits(int* out) {
 // act / mask_in: 0 linear, 1 relu, 2 tanh, 3 sigmoid; anything else returns -8).  mode 0 train (part / rec written,
 // iterations += 1), 1 eval (metrics += loss, correct, count), 2 predict (probs).  step: device word
 // holding the number of completed training steps, required when a layer drops (Dropout is the identity
-// in modes 1 and 2).
-TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const float* w, const float* x,
-                              int x_stride, int in0, int n_in0, const int* img, const int* y, float* part, int npart,
-                              float* rec,
-                              int nrec, float* metrics, long long* iterations, const long long* step, float scale,
-                              float* probs,
-                              int probs_softmax, long long* stamps, hipStream_t stream) {
+// in modes 1 and 2).  ls (nullable): the loss head's spec of tde_smallnet_step_loss.
+static int sn_step_launch(const int* layers, int nl, int mode, int B, const float* w, const float* x, int x_stride,
+                          int in0, int n_in0, const int* img, const int* y, float* part, int npart, float* rec,
+                          int nrec, float* metrics, long long* iterations, const long long* step, float scale,
+                          float* probs, int probs_softmax, long long* stamps, const LossSpec* ls,
+                          hipStream_t stream) {
   if (nl < 1 || nl > kSnMaxLayers || B <= 0) return -1;
   if (mode == 0 && (!part || !rec || !iterations || nrec < 2)) return -2;
   SnArgs a{};
@@ -1305,9 +1333,40 @@ TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const 
     return e ? atoi(e) : 3;
   }();
   a.mfma = mfma;
-  smallnet_step_kernel<<<B, kSnThreads, 0, stream>>>(a);
+  if (ls) {
+    SnLossArgs la{};
+    static_cast<SnArgs&>(la) = a;
+    la.ls = *ls;
+    smallnet_step_loss_kernel<<<B, kSnThreads, 0, stream>>>(la);
+  } else {
+    smallnet_step_kernel<<<B, kSnThreads, 0, stream>>>(a);
+  }
   TDE_LAUNCH_CHECK();
   return 0;
+}
+
+TDE_API int tde_smallnet_step(const int* layers, int nl, int mode, int B, const float* w, const float* x,
+                              int x_stride, int in0, int n_in0, const int* img, const int* y, float* part, int npart,
+                              float* rec,
+                              int nrec, float* metrics, long long* iterations, const long long* step, float scale,
+                              float* probs,
+                              int probs_softmax, long long* stamps, hipStream_t stream) {
+  return sn_step_launch(layers, nl, mode, B, w, x, x_stride, in0, n_in0, img, y, part, npart, rec, nrec, metrics,
+                        iterations, step, scale, probs, probs_softmax, stamps, nullptr, stream);
+}
+
+// The step with a non-trivial loss head (smallnet_step_loss_kernel, every mode): label smoothing `smooth` in
+// [0, 1) and the per-class row weights class_w ([classes] device floats, or null: every weight 1).  A bad spec
+// returns -9.
+TDE_API int tde_smallnet_step_loss(const int* layers, int nl, int mode, int B, const float* w, const float* x,
+                                   int x_stride, int in0, int n_in0, const int* img, const int* y, float* part,
+                                   int npart, float* rec, int nrec, float* metrics, long long* iterations,
+                                   const long long* step, float scale, float* probs, int probs_softmax,
+                                   long long* stamps, float smooth, const float* class_w, hipStream_t stream) {
+  const LossSpec ls{smooth, class_w != nullptr, class_w};
+  if (!loss_spec_ok(ls)) return -9;
+  return sn_step_launch(layers, nl, mode, B, w, x, x_stride, in0, n_in0, img, y, part, npart, rec, nrec, metrics,
+                        iterations, step, scale, probs, probs_softmax, stamps, &ls, stream);
 }
 
 // ranges: nr x {part_lo, n, flat_off}; dense: nd x {In, Co, xo, go, w_off, b_off, blk0, nblk}.

@@ -125,6 +125,10 @@ _HIP_PROTOS = {
     "tde_smallnet_limits": (i32, [p]),
     "tde_smallnet_step": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p, i32,
                                 p, p]),
+    "tde_smallnet_step_loss": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p,
+                                     i32, p, f32, p, p]),
+    # softmax-CE with label smoothing / class weights (csrc/kernels/losshead.hip)
+    "tde_xent_spec": (i32, [p, i64, p, i32, i32, f32, p, i64, i32, p, p, i32, p, f32, p, p]),
     "tde_smallnet_wgrad": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p, i32, i32, f32, f32,
                                  f32, f32, f32, p]),
     "tde_smallnet_wgrad_sched": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, i32, f32, f32,

@@ -19,10 +19,15 @@ class Mean:
     name = "loss"
 
 
-def resolve(metrics):
+def resolve(metrics, loss=None):
+    """``"categorical_accuracy"`` is ``"accuracy"``'s alias under the categorical loss: the one-hot labels are
+    class indices by the time a plan sees them, and the accuracy is argmax against the index either way."""
+    from .losses import CategoricalCrossentropy
     out = []
     for m in metrics or []:
         if m in ("accuracy", "acc", "sparse_categorical_accuracy") or isinstance(m, SparseCategoricalAccuracy):
+            out.append("accuracy")
+        elif m == "categorical_accuracy" and isinstance(loss, CategoricalCrossentropy):
             out.append("accuracy")
         else:
             raise ValueError(f"unsupported metric {m!r}")

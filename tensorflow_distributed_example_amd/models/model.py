@@ -89,16 +89,19 @@ class Model:
             out += [s for s in lst if s is not self._store]
         return out
 
-    def _program(self, kind, global_batch, single_replica=False):
+    def _program(self, kind, global_batch, single_replica=False, class_weight=False):
+        """``class_weight``: the training program of ``fit(class_weight=)`` -- "has class weights" is part of the
+        key, the weights themselves live in the plans' tables (``Program.set_class_weight``)."""
         strategy = _SingleReplica(self._store.device) if single_replica else self._strategy
+        class_weight = bool(class_weight and kind == "train")
         key = (kind, int(global_batch), id(strategy) if not single_replica else "single",
-               self.steps_per_execution if kind == "train" else 1)
+               self.steps_per_execution if kind == "train" else 1) + (("class_weight",) if class_weight else ())
         prog = self._programs.get(key)
         if prog is None:
             if kind == "train" and self.optimizer is None:
                 raise RuntimeError("You must compile your model before training/testing.")
             prog = RN.Program(self, strategy, global_batch, training=(kind == "train"),
-                              steps_per_execution=self.steps_per_execution)
+                              steps_per_execution=self.steps_per_execution, class_weight=class_weight)
             self._programs[key] = prog
         return prog
 
@@ -225,8 +228,11 @@ class Model:
         self._require_built()
         self.optimizer = OP.get(optimizer)
         self.loss = LS.get(loss)
+        if weighted_metrics:
+            raise NotImplementedError("compile(weighted_metrics=...) is not supported: there is no per-row weight "
+                                      "feed; metrics= are unweighted, as fit(class_weight=) leaves them")
         self.compiled_metrics = list(metrics or [])
-        self._metric_names = MT.resolve(metrics)
+        self._metric_names = MT.resolve(metrics, self.loss)
         if steps_per_execution is not None:
             self.steps_per_execution = int(steps_per_execution)
         if DS.has_strategy():
@@ -238,11 +244,18 @@ class Model:
         self._programs = {}
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose="auto", callbacks=None, validation_data=None,
-            steps_per_epoch=None, initial_epoch=0, shuffle=True, validation_steps=None, validation_freq=1, **kw):
+            steps_per_epoch=None, initial_epoch=0, shuffle=True, validation_steps=None, validation_freq=1,
+            class_weight=None, sample_weight=None, **kw):
+        if sample_weight is not None:
+            raise NotImplementedError("fit(sample_weight=...) is not supported: there is no per-row weight feed; "
+                                      "class_weight= is the supported form")
         return E.fit(self, x, y, batch_size, epochs, verbose, callbacks, validation_data, steps_per_epoch,
-                     initial_epoch, shuffle, validation_steps, validation_freq)
+                     initial_epoch, shuffle, validation_steps, validation_freq, class_weight=class_weight)
 
-    def evaluate(self, x=None, y=None, batch_size=None, verbose="auto", steps=None, return_dict=False, **kw):
+    def evaluate(self, x=None, y=None, batch_size=None, verbose="auto", steps=None, return_dict=False,
+                 sample_weight=None, **kw):
+        if sample_weight is not None:
+            raise NotImplementedError("evaluate(sample_weight=...) is not supported: there is no per-row weight feed")
         return E.evaluate(self, x, y, batch_size, verbose, steps, return_dict)
 
     def predict(self, x, batch_size=None, verbose=0, steps=None, **kw):

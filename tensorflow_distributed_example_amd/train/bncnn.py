@@ -26,7 +26,7 @@ import torch
 
 from .. import _native as N
 from .. import backend as Kb
-from ..losses import SparseCategoricalCrossentropy
+from .. import losses as LS
 from ..models import layers as L
 from ..ops.kernels import BnOpt, opt_hyper, opt_slots
 from .program import OptimizerKernel, ReplicaPlan
@@ -93,7 +93,7 @@ def _chain(model):
 
 def match_bncnn(model, loss):
     """dict(convs=[(conv, bn)], dense=(dense, bn, dropout|None), head=dense) or None."""
-    if not isinstance(loss, SparseCategoricalCrossentropy):
+    if not LS.is_softmax_ce(loss):
         return None
     chain = _chain(model)
     if not chain:
@@ -151,6 +151,11 @@ def match_bncnn(model, loss):
         import warnings
         warnings.warn(f"model {model.name!r}: no fused BN-CNN step ({'; '.join(too_wide)}); running the per-layer "
                       "kernel plan")
+        return None
+    if LS.nontrivial(loss):
+        import warnings
+        warnings.warn(f"model {model.name!r}: the fused BN-CNN step has no loss head for {LS.spec_reason(loss)}; "
+                      "running the per-layer kernel plan")
         return None
     return dict(convs=convs, dense=(d, bn_d, drop), head=head)
 

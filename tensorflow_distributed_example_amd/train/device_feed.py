@@ -20,6 +20,8 @@ import os
 import numpy as np
 import torch
 
+from .. import losses as LS
+
 
 class DeviceFeed:
     @staticmethod
@@ -37,11 +39,13 @@ class DeviceFeed:
         x, y = cols
         if not (isinstance(x, np.ndarray) and isinstance(y, np.ndarray)):
             return None
-        if x.dtype.kind not in "fiu" or y.dtype.kind not in "iu" or len(x) == 0:
+        # the categorical loss: one-hot rows [n, classes] of any numeric dtype, cached as their int32 indices
+        onehot = isinstance(prog.model.loss, LS.CategoricalCrossentropy)
+        if x.dtype.kind not in "fiu" or y.dtype.kind not in ("biuf" if onehot else "iu") or len(x) == 0:
             return None
         n = len(x)
         per = int(np.prod(prog.x_shape))
-        if len(y) != n or x.size != n * per or y.size != n or n >= 2 ** 31:
+        if len(y) != n or x.size != n * per or (y.size != n and not onehot) or n >= 2 ** 31:
             return None
         if not DeviceFeed.row_ok(per, prog.x_ring[0].dtype):
             return None
@@ -63,16 +67,19 @@ class DeviceFeed:
         self.it = None
         self.n = len(x)
         self.per = int(np.prod(prog.x_shape))
-        self.x_host, self.y_host = x, y      # host copies for partial batches
         SB = prog.S * prog.B
         # the uploaded columns stay with the program: a later fit() over the same cached arrays reuses them
         cached = getattr(prog, "_device_cache", None)
         if cached is not None and cached[0] is x and cached[1] is y:
-            cols = cached[2]
+            cols, yi = cached[2], cached[3]
         else:
             prog._device_cache = None
             xf = np.ascontiguousarray(x.reshape(self.n, self.per), dtype=np.float32)
-            yi = np.ascontiguousarray(y.reshape(-1), dtype=np.int32)
+            if isinstance(prog.model.loss, LS.CategoricalCrossentropy):
+                # one-hot rows -> class indices, once for the whole cache (raises on a row that is not one-hot)
+                yi = LS.onehot_to_index(y, prog.model.output_shape[-1])
+            else:
+                yi = np.ascontiguousarray(y.reshape(-1), dtype=np.int32)
             cols = []
             for r, d in enumerate(prog.devices):
                 with torch.cuda.device(d):
@@ -85,7 +92,8 @@ class DeviceFeed:
                     elif ring_dt != torch.float32:
                         xd = xd.to(ring_dt)
                     cols.append((xd, torch.from_numpy(yi).to(d)))
-            prog._device_cache = (x, y, cols)
+            prog._device_cache = (x, y, cols, yi)
+        self.x_host, self.y_host = x, yi      # host copies for partial batches (the labels as class indices)
         self.dev = []
         for r, d in enumerate(prog.devices):
             xd, yd = cols[r]

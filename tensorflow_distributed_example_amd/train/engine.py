@@ -16,6 +16,7 @@ import torch
 
 from ..data.dataset import Dataset, _Batch
 from ..data.distributed import DistributedDataset
+from .. import losses as LS
 from ..metrics import logs_from
 from . import callbacks as CB
 from ..utils import fault
@@ -73,14 +74,20 @@ def _stack_steps(batches):
 
 
 def fit(model, x=None, y=None, batch_size=None, epochs=1, verbose="auto", callbacks=None, validation_data=None,
-        steps_per_epoch=None, initial_epoch=0, shuffle=True, validation_steps=None, validation_freq=1):
+        steps_per_epoch=None, initial_epoch=0, shuffle=True, validation_steps=None, validation_freq=1,
+        class_weight=None):
     strategy = model._strategy
+    ncls = model.output_shape[-1]
+    # Keras 3: w_i = class_weight.get(y_i, 1.0), on the training loss and gradient only
+    cw_table = LS.class_weight_table(class_weight, ncls) if class_weight is not None else None
     ds = _to_dataset(x, y, batch_size, shuffle)
     gb = _global_batch_of(ds)
     if gb is None:
         raise ValueError("the training dataset must be batched (dataset.batch(GLOBAL_BATCH_SIZE))")
     dds = ds if isinstance(ds, DistributedDataset) else strategy.experimental_distribute_dataset(ds)
-    prog = model._program("train", gb)
+    prog = model._program("train", gb, class_weight=cw_table is not None)
+    if cw_table is not None:
+        prog.set_class_weight(cw_table)   # in place: a program that has its graphs replays them
     S = prog.S
     in_shape = prog.x_shape
     verbose = 1 if verbose == "auto" else verbose
@@ -111,7 +118,7 @@ def fit(model, x=None, y=None, batch_size=None, epochs=1, verbose="auto", callba
         per = []
         for elem in b:
             xx, yy = _split_xy(elem)
-            per.append((_fix_x(xx, in_shape), np.asarray(yy).reshape(-1) if not torch.is_tensor(yy) else yy.reshape(-1)))
+            per.append((_fix_x(xx, in_shape), LS.labels_for(model.loss, yy, ncls)))
         return per
 
     logs = {}
@@ -211,11 +218,13 @@ def evaluate(model, x=None, y=None, batch_size=None, verbose="auto", steps=None,
     prog.on_weights_loaded()
     prog.reset_metrics()
     in_shape = prog.x_shape
+    ncls = model.output_shape[-1]
     n = 0
     for b in dds:
         per = []
         for elem in b:
             xx, yy = _split_xy(elem)
+            yy = LS.labels_for(model.loss, yy, ncls)
             per.append((_fix_x(xx, in_shape), np.asarray(yy).reshape(-1)))
         prog.eval_batch(per)
         n += 1

@@ -194,9 +194,11 @@ class LayerwisePlan(PG.ReplicaPlan):
         strip = PG._last_softmax(m, self.loss)
         if last_layer.activation not in (None, "softmax") or (last_layer.activation == "softmax") != strip:
             raise Unsupported("head must be Dense logits with from_logits=True or Dense(softmax) with probabilities")
-        from ..losses import SparseCategoricalCrossentropy
-        if not isinstance(self.loss, SparseCategoricalCrossentropy):
+        from .. import losses as LS
+        if not LS.is_softmax_ce(self.loss):
             raise Unsupported(f"loss {type(self.loss).__name__} has no fused HIP kernel")
+        if LS.nontrivial(self.loss):   # label smoothing / class weights: the head launches losshead.hip's kernel
+            self._init_loss_spec(self.loss, last_layer.units)
 
         chains = elementwise_chains(nodes)    # stage ids and absorbed [Add] [ReLU] [Dropout] nodes
         for i, (layer, ins, out) in enumerate(nodes):
@@ -936,8 +938,9 @@ class _Head(_Stage):
         self.H = tin.shape[0]
         self.W = st.view(self.wname)
         self.f32 = plan.f32
+        # a non-trivial loss spec takes the general path, with the spec kernel in place of xent
         self.fused = (not self.f32 and not plan.det and self.C <= 16 and self.H <= 256 and self.H % 4 == 0
-                      and os.environ.get("TDE_FUSED_HEAD", "1") != "0")
+                      and not plan.loss_spec and os.environ.get("TDE_FUSED_HEAD", "1") != "0")
         self.shadows = {} if (self.fused or self.f32) else {self.wname: ("row", "col") if self.need_dgrad else ("col",)}
         self.pre = None   # absorbed Dense: its ReLU mask and bias gradient are applied by the head launch
 
@@ -980,9 +983,30 @@ class _Head(_Stage):
             K.head_xent(h, self.W, self.b, p._labels, B=B, scale=1.0, compute_grad=False,
                         probs=self.probs[: B * self.C].view(B, self.C), probs_are_logits=self.logits_out)
 
+    def _spec_xent(self, p, B, mode):
+        """The softmax-CE launch of a non-trivial loss spec (ops/loss_ops.py); the class weights apply to the
+        training loss and gradient only."""
+        from ..ops import loss_ops as OL
+        if mode == "train":
+            OL.xent_spec(self.logits, p._labels, B, self.C, smooth=p.smooth, class_w=p.class_w, scale=p.scale,
+                         dlogits=self.dlogits, metrics=p.metrics, iterations=p.iterations)
+        elif mode == "eval":
+            OL.xent_spec(self.logits, p._labels, B, self.C, smooth=p.smooth, scale=p.scale, metrics=p.metrics,
+                         bf16=not self.f32)
+        else:
+            OL.xent_spec(self.logits, p._labels, B, self.C, smooth=p.smooth, probs=self.probs,
+                         probs_are_logits=self.logits_out, bf16=not self.f32)
+
     def fwd(self, p, B, training, mode="train"):
         if self.fused:
             self._fused_fwd(p, B, mode)
+            return
+        if p.loss_spec:
+            if self.f32:
+                O32.dense_fwd(self.inp.root().buf, self.W, B, self.logits, bias=self.b)
+            else:
+                O.dense_fwd(self.inp.root().buf, self.Wt, B, logits=self.logits, bias=self.b)
+            self._spec_xent(p, B, mode)
             return
         if self.f32:
             O32.dense_fwd(self.inp.root().buf, self.W, B, self.logits, bias=self.b)

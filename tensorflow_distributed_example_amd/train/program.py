@@ -69,6 +69,32 @@ class ReplicaPlan:
         self._reg_stale = True     # the penalty partials are older than the weights
         if optimizer is not None:
             optimizer._plan_built = True   # the per-variable decay is settled: exclude_from_weight_decay raises
+        # the loss head's spec (losses.py): label smoothing by value, and -- in a program built for
+        # fit(class_weight=) -- the table of row weights by class, which ``set_class_weight`` rewrites in place
+        self.smooth = 0.0
+        self.class_w = None
+
+    def _init_loss_spec(self, loss, classes):
+        """Take the spec of ``loss`` (a plan that runs a non-trivial one calls this from its constructor)."""
+        from .. import losses as LS
+        self.smooth = LS.smoothing(loss)
+        if LS.class_weighted(loss):
+            self.class_w = torch.ones(int(classes), dtype=torch.float32, device=self.device)
+
+    @property
+    def loss_spec(self):
+        """A non-trivial spec: the plan launches the loss-head variants (csrc/include/tde_loss.h)."""
+        return self.smooth != 0.0 or self.class_w is not None
+
+    def set_class_weight(self, table):
+        """``fit(class_weight=)``: the float32 [classes] table into the plan's own, in place -- a captured step
+        reads the new weights at its next replay."""
+        if self.class_w is None:
+            raise RuntimeError(f"the {self.kind} plan was not built for class weights")
+        t = torch.as_tensor(table, dtype=torch.float32)
+        if t.numel() != self.class_w.numel():
+            raise ValueError(f"class-weight table of {t.numel()} entries, plan has {self.class_w.numel()} classes")
+        self.class_w.copy_(t.reshape(-1))
 
     def reset_metrics(self):
         self.metrics.zero_()
@@ -216,6 +242,9 @@ class ReferencePlan(ReplicaPlan):
         self.loss = loss
         self.strip_softmax = _last_softmax(model, loss)
         self.rng = Kb.make_generator(1234)
+        from .. import losses as LS
+        if LS.nontrivial(loss):
+            self._init_loss_spec(loss, model.output_shape[-1])
 
     def _weights(self, wl):
         W = {}
@@ -255,7 +284,10 @@ class ReferencePlan(ReplicaPlan):
         W = self._weights(wl)
         updates = []
         out = self._forward(x, W, True, updates)
-        ls = self.loss.per_sample(y, out, pred_is_logits=self.strip_softmax)
+        if self.class_w is not None:   # the training loss and gradient only
+            ls = self.loss.per_sample(y, out, pred_is_logits=self.strip_softmax, class_weight=self.class_w)
+        else:
+            ls = self.loss.per_sample(y, out, pred_is_logits=self.strip_softmax)
         (ls.sum() * self.scale).backward()
         with torch.no_grad():
             self.store.g.add_(wl.grad)
@@ -517,12 +549,13 @@ class OptimizerKernel:
 
 def match_convnet(model, loss):
     """Pattern of the DWK/TF2M small CNN: Conv2D(3x3,relu,bias) on 1 channel ·
-    MaxPooling2D(2) · Flatten · Dense(bias[,relu]) · Dense(bias[,softmax]) + SCCE."""
-    from ..losses import SparseCategoricalCrossentropy
+    MaxPooling2D(2) · Flatten · Dense(bias[,relu]) · Dense(bias[,softmax]) + softmax-CE with a trivial spec
+    (the sparse loss, or the categorical one without label smoothing; no class weights)."""
+    from .. import losses as LS
     ls = [l for l in model.layers if not isinstance(l, L.InputLayer)]
     if ls and isinstance(ls[0], L.Reshape) and len(ls[0].target_shape) == 3:
         ls = ls[1:]
-    if len(ls) != 5 or not isinstance(loss, SparseCategoricalCrossentropy):
+    if len(ls) != 5 or not LS.is_softmax_ce(loss):
         return None
     c, p, f, d1, d2 = ls
     ok = (isinstance(c, L.Conv2D) and c.kernel_size == (3, 3) and c.strides == (1, 1) and c.padding == "valid"
@@ -536,6 +569,11 @@ def match_convnet(model, loss):
         return None
     if (d2.activation == "softmax") == bool(loss.from_logits):
         return None  # probabilities fed to from_logits=True (or logits w/o from_logits): not fusable
+    if LS.nontrivial(loss):
+        import warnings
+        warnings.warn(f"model {model.name!r}: the fused small-CNN step has no loss head for "
+                      f"{LS.spec_reason(loss)}; running the per-layer kernel plan")
+        return None
     force_gen = os.environ.get("TDE_CONVNET_GENERIC", "0") == "1"   # A/B: the generic kernels at any width
     if c.filters != 32 or d1.units != 64 or force_gen:
         # the hand-tuned step is the reference's Conv2D(32)/Dense(64) (distributed_with_keras.py:34,37);
@@ -1049,8 +1087,13 @@ class ConvNetGenPlan(SmallCnnPlan):
 
 
 # ---------------------------------------------------------------------------------------
-def make_plan(model, store, device, batch, global_batch, optimizer, loss, prefer=None):
+def make_plan(model, store, device, batch, global_batch, optimizer, loss, prefer=None, class_weight=False):
+    """``class_weight``: the program is built for ``fit(class_weight=)`` -- the plan keeps a table of row weights
+    by class (a non-trivial loss spec: the small-net, layer-wise and reference plans)."""
     device = torch.device(device)
+    if class_weight:
+        from .. import losses as LS
+        loss = LS.with_class_weight(loss)
     prefer = prefer or os.environ.get("TDE_EXECUTOR")
     if device.type == "cuda" and prefer != "reference":
         pat = match_convnet(model, loss)

@@ -107,8 +107,10 @@ def _same_device_pair(src, ring):
 
 
 class Program:
-    def __init__(self, model, strategy, global_batch, training, steps_per_execution=1):
+    def __init__(self, model, strategy, global_batch, training, steps_per_execution=1, class_weight=False):
         self.model = model
+        # built for fit(class_weight=): every plan keeps a table of row weights by class (``set_class_weight``)
+        self.class_weight = bool(class_weight and training)
         self.strategy = strategy
         self.world = strategy.num_replicas_in_sync
         if global_batch % self.world:
@@ -119,7 +121,8 @@ class Program:
         self.stores = model._replica_stores(strategy)
         self.devices = list(strategy.local_devices)
         opt = model.optimizer if training else None
-        self.plans = [PG.make_plan(model, st, dev, self.B, global_batch, opt, model.loss)
+        self.plans = [PG.make_plan(model, st, dev, self.B, global_batch, opt, model.loss,
+                                   class_weight=self.class_weight)
                       for st, dev in zip(self.stores, self.devices)]
         self.comm = strategy.comm if self.world > 1 else None
         self.grad_comm = self.comm   # carries the gradient bucket (may differ from self.comm: _pick_step_mode)
@@ -257,6 +260,13 @@ class Program:
     @property
     def plan_kind(self):
         return self.plans[0].kind
+
+    def set_class_weight(self, table):
+        """The float32 [classes] table of ``fit(class_weight=)`` into every plan's own, in place: the captured
+        graphs stay as they are and read the new weights at the next replay."""
+        for p in self.plans:
+            with _ctx(p.device):
+                p.set_class_weight(table)
 
     # ------------------------------------------------------------------ staging
     def stage(self, per_replica_steps):

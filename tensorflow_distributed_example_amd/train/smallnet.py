@@ -4,7 +4,8 @@ Model families: BASELINE.json config 2 (MNIST LeNet-5, ``zoo.lenet5``) and confi
 (``tf2_mnist_distributed.py``'s plumbing model, ``zoo.mnist_mlp``); any Sequential chain of
 ``Conv2D(stride 1, same/valid, act) [MaxPooling2D(2) | AveragePooling2D(2)]`` stages,
 ``Flatten``/``Reshape``, ``Dense(act)`` layers and a ``Dense`` head (logits, or softmax fed to the
-probability form of ``SparseCategoricalCrossentropy``) whose per-image activations fit in one
+probability form of ``SparseCategoricalCrossentropy`` / ``CategoricalCrossentropy``; with label smoothing
+or ``fit(class_weight=)`` the step runs its loss-head variant, ``smallnet_step_loss_kernel``) whose per-image activations fit in one
 workgroup's LDS; ``act`` is linear, relu, tanh or sigmoid, on the layer or as a standalone
 ``Activation`` behind a linear one (``zoo.lenet5_classic``: LeCun's tanh / average-pool LeNet-5).  The
 backward needs nothing stored for them: each gradient overwrites the activation it belongs to, and the
@@ -38,7 +39,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from ..losses import SparseCategoricalCrossentropy
+from .. import losses as LS
 from ..models import layers as L
 from ..ops.kernels import OptHyper, lr_sched, opt_hyper, opt_slots
 from .elementwise_ids import dropout_ids
@@ -78,7 +79,7 @@ def match_smallnet(model, loss):
     """Per-layer description of a supported model, or None.  One entry per Conv2D / pooling layer / Dense;
     ``relu`` is the entry's activation code (LINEAR, RELU, TANH, SIGMOID), ``drop`` the Dropout layer applied
     to the entry's output (after its activation), or None."""
-    if not isinstance(loss, SparseCategoricalCrossentropy):
+    if not LS.is_softmax_ce(loss):   # either class, any spec: the step kernel has a loss-head variant
         return None
     chain = _chain(model)
     if not chain:
@@ -255,6 +256,8 @@ class SmallNetPlan(ReplicaPlan):
         self.dense = np.ascontiguousarray(np.array(dense, dtype=np.int32))
         self.ncls = spec[-1]["outp"][2]
         self.probs_softmax = int(spec[-1]["layer"].activation == "softmax")
+        if LS.nontrivial(loss):
+            self._init_loss_spec(loss, self.ncls)
         dev = self.device
         B = self.B
         self.part = torch.zeros(B, self.npart, dtype=torch.float32, device=dev)
@@ -296,13 +299,19 @@ class SmallNetPlan(ReplicaPlan):
         if y is not None and y.dtype != torch.int32:
             raise ValueError("labels must be int32")
         train = mode == 0
-        rc = self.lib.tde_smallnet_step(
-            self.layers.ctypes.data, len(self.layers), mode, B, self.store.w.data_ptr(), x.data_ptr(),
-            self.x_stride, self.in0, self.n_in0, self.img.ctypes.data, N.ptr(y),
-            self.part.data_ptr() if train else None, self.npart,
-            self.rec.data_ptr() if train else None, self.nrec, self.metrics.data_ptr(),
-            self.iterations.data_ptr(), N.ptr(self.step_word), float(self.scale), N.ptr(probs), self.probs_softmax, N.ptr(self.stamps),
-            N.stream_ptr())
+        args = (self.layers.ctypes.data, len(self.layers), mode, B, self.store.w.data_ptr(), x.data_ptr(),
+                self.x_stride, self.in0, self.n_in0, self.img.ctypes.data, N.ptr(y),
+                self.part.data_ptr() if train else None, self.npart,
+                self.rec.data_ptr() if train else None, self.nrec, self.metrics.data_ptr(),
+                self.iterations.data_ptr(), N.ptr(self.step_word), float(self.scale), N.ptr(probs),
+                self.probs_softmax, N.ptr(self.stamps))
+        if self.loss_spec:
+            # the weights apply to the training loss and gradient only
+            rc = self.lib.tde_smallnet_step_loss(*args, float(self.smooth), N.ptr(self.class_w) if train else None,
+                                                 N.stream_ptr())
+            N.check(rc, "tde_smallnet_step_loss")
+            return
+        rc = self.lib.tde_smallnet_step(*args, N.stream_ptr())
         N.check(rc, "tde_smallnet_step")
 
     def train_step(self, x, y, B=None):
