@@ -57,16 +57,25 @@ def eager_time(fn, reps=500):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-def stamps_summary(st, nslots):
-    st = st.cpu().numpy().astype(np.float64)
-    used = st[:, :nslots]
+def stamps_summary(st, slots):
+    """Per slot (a column of ``st``) min / median / max over the workgroups that wrote all of ``slots``, from the
+    earliest workgroup's slot 0.  Slots no workgroup wrote (a library without them) are left out."""
+    st = np.asarray(st, dtype=np.float64)
+    slots = [i for i in (range(slots) if isinstance(slots, int) else slots) if (st[:, i] > 0).any()]
+    used = st[:, slots]
     used = used[(used > 0).all(axis=1)]
     if len(used) == 0:
         return {}
     t0 = used[:, 0].min()
     rel = (used - t0) * 0.01  # 100 MHz ticks -> us
-    return {f"slot{i}": {"min": round(float(rel[:, i].min()), 2), "med": round(float(np.median(rel[:, i])), 2),
-                         "max": round(float(rel[:, i].max()), 2)} for i in range(nslots)}
+    return {f"slot{s}": {"min": round(float(rel[:, k].min()), 2), "med": round(float(np.median(rel[:, k])), 2),
+                         "max": round(float(rel[:, k].max()), 2)} for k, s in enumerate(slots)}
+
+
+# the float32 backward's slots in time order: 8..12 (operands landed, staging barrier passed, logit partials
+# published, dlogits published, G / G^T stored) are its second bank of 8, which lies behind the first bank of
+# all workgroups (csrc/include/tde_convnet.h: stamp_fine)
+BWD_SLOTS = [0, 1, 8, 9, 10, 11, 12, 2, 3, 4, 5]
 
 
 def main():
@@ -130,15 +139,18 @@ def main():
     plan.finish()
     plan.set_step_mode("plain")
     st = torch.zeros(4096 * 8, dtype=torch.int64, device="cuda")
-    for name, f, ns in [("convnet_fwd", k_fwd, 5), ("convnet_bwd_head", k_bwd, 6)]:
+    nwg_bwd = plan.P + 1   # 16 slots per workgroup of the backward: 2 banks x 8, 4096 x 8 values hold both
+    for name, f, ns in [("convnet_fwd", k_fwd, 5), ("convnet_bwd_head", k_bwd, BWD_SLOTS)]:
         st.zero_()
         f()
         torch.cuda.synchronize()
         st.zero_()
         f(stamps=st)
         torch.cuda.synchronize()
-        out[f"stamps_{name}"] = stamps_summary(st.view(-1, 8), ns)
         rows = st.view(-1, 8).cpu().numpy().astype(np.float64)
+        if name == "convnet_bwd_head":
+            rows = np.concatenate([rows[:nwg_bwd], rows[nwg_bwd:2 * nwg_bwd]], axis=1)
+        out[f"stamps_{name}"] = stamps_summary(rows, ns)
         head = rows[rows[:, 7] > 0]
         if len(head):   # the backward's head workgroup: start and end, on the trunk's clock
             t0 = rows[rows[:, 0] > 0, 0].min()

@@ -373,6 +373,14 @@ __device__ __forceinline__ void zero_other_parity(const BwdArgs& a, int tid) {
   for (int i = beg + tid; i < end; i += 1024) reinterpret_cast<float4*>(a.hzero)[i] = float4{0.f, 0.f, 0.f, 0.f};
 }
 
+// The same with the launch's workgroup count given (a constant in the fixed-geometry form: no runtime division)
+__device__ __forceinline__ void zero_other_parity_n(const BwdArgs& a, int tid, int nwg) {
+  const int n4 = (int)(((a.hrep - 1) * a.hrep_stride + (long long)a.B * HD) / 4);
+  const int per = (n4 + nwg - 1) / nwg, beg = blockIdx.x * per;
+  const int end = min(n4, beg + per);
+  for (int i = beg + tid; i < end; i += 1024) reinterpret_cast<float4*>(a.hzero)[i] = float4{0.f, 0.f, 0.f, 0.f};
+}
+
 // An opaque copy of threadIdx.x for the chunk loops of the backward: the addresses computed from it (all
 // loop-invariant: one per load and per LDS access) are computed again in each iteration and not kept in
 // registers across the loop, where they pushed the kernels into scratch.
@@ -502,6 +510,67 @@ __device__ __forceinline__ void head_logits_ce(const BwdArgs& a, int nb, const H
   lds_barrier();
 }
 
+// Fine phase stamps of the float32 backward, slots 8..15: a second bank of kMaxStamps slots per workgroup
+// behind the first one (stamps[(workgroups + blockIdx.x) * kMaxStamps + slot - 8]), so a stamp buffer given to
+// that kernel holds 2 * workgroups * kMaxStamps values.  8: chunk operands landed, 9: staging barrier passed,
+// 10: logit partials published, 11: dlogits published, 12: G / G^T stored (the wave's LDS stores done).
+__device__ __forceinline__ void stamp_fine(long long* st, int slot) {
+  if (st && threadIdx.x == 0) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    st[(size_t)(gridDim.x + blockIdx.x) * kMaxStamps + slot - kMaxStamps] = (long long)__builtin_amdgcn_s_memrealtime();
+  }
+}
+
+// The same on all 16 waves (the LEAN form of the float32 kernels): every K-quarter wave publishes its
+// partial (kq == 0 into part0: [4 rt][4 i][64 lanes] floats outside the head areas; kq > 0 into l.part in
+// the same [i][lane] order, one bank per lane), then wave (rt = wave & 3, i = wave >> 2) sums element i of
+// the four partials in the order ((kq0 + kq1) + kq2) + kq3 and does the one softmax row set
+// rt*16 + 4*fq + i: one iteration per wave, not four on four waves while twelve wait.
+// METRICS = false (the trunk workgroups): loss / arg-max / count are not computed at all.
+template <bool METRICS>
+__device__ __forceinline__ void head_logits_ce16(const BwdArgs& a, int nb, const HeadLds& l, float* part0, int lane,
+                                                 int wave, float& la, float& ca, float& na) {
+  const int fr = lane & 15, fq = lane >> 4, C = a.C;
+  {
+    const int rt = wave & 3, kq = wave >> 2;
+    f32x4 lg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = kq * 16; k < kq * 16 + 16; k += 4)
+      lg = mfma_f32x4(l.hs[(rt * 16 + fr) * HS + k + fq], l.w2s[(k + fq) * W2S + fr], lg);
+    float* dst = (kq == 0 ? part0 : l.part + (kq - 1) * 1024) + rt * 256 + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dst[i * 64] = lg[i];
+  }
+  lds_barrier();
+  stamp_fine(a.stamps, 10);
+  {
+    const int rt = wave & 3, i = wave >> 2;
+    const int o = rt * 256 + i * 64 + lane;
+    const float p0 = part0[o], p1 = l.part[o], p2 = l.part[1024 + o], p3 = l.part[2048 + o];
+    const float lgi = ((p0 + p1) + p2) + p3;
+    const int r = rt * 16 + fq * 4 + i;
+    const bool valid = r < nb;
+    const bool cv = fr < C;
+    const float z = cv ? lgi + l.b2s[fr] : -3.0e38f;
+    const float m = row16_max(z);
+    const float e = cv ? __expf(z - m) : 0.f;
+    const float s = row16_sum(e);
+    const float pr = e / s;
+    const int label = l.labs[r];
+    if (METRICS) {
+      const int amx = row16_min(cv && z == m ? fr : 64);
+      const float zl = __shfl(z, (lane & ~15) | (label & 15), 64);
+      if (valid && fr == 0) {
+        la += __logf(s) + m - zl;
+        ca += (amx == label) ? 1.f : 0.f;
+        na += 1.f;
+      }
+    }
+    l.dls[r * DLS + fr] = (valid && cv) ? (pr - (fr == label ? 1.f : 0.f)) * a.scale : 0.f;
+  }
+  lds_barrier();
+}
+
 // dH tile of this wave (rows rt*16.., units ut*16.., rt = wave>>2, ut = wave&3) = dl . W2^T, masked
 // by h > 0 and rows < nb.  Lane holds dH[rt*16 + 4fq + i][ut*16 + fr].
 __device__ __forceinline__ f32x4 head_dh(const BwdArgs& a, int nb, const HeadLds& l, int lane, int wave) {
@@ -532,7 +601,8 @@ __device__ __forceinline__ long long head_var(const BwdArgs& a, int tid, int i) 
 
 // The head workgroup: loss / accuracy, dW2 = h^T . dl, db2, db1 over all chunks, then stored (MODE 0)
 // or updated (fused step; with the previous step's deferred conv update and the flags).
-// db1p: 256 floats of LDS scratch outside the head areas.
+// db1p: 256 floats of LDS scratch outside the head areas (LEAN: 1024, which also hold the logits' first
+// K-quarter partial inside the chunk loop and the 16 waves' metrics after it).
 // LEAN (the float32 kernels, which must stay out of scratch): thread indices from opaque_tid() inside the
 // chunk loop and at the update, replica slots by switch.
 template <int MODE, bool LEAN = false>
@@ -577,7 +647,9 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
     head_stage(a, hv, b1v, hr, hc4, nb, l.hs);
     if (tid < 64) l.labs[tid] = lab;
     lds_barrier();
-    head_logits_ce(a, nb, l, lane, wave, la, ca, na);
+    // LEAN: softmax-CE on all 16 waves (partial 0 in the otherwise unused db1p area until the loop ends)
+    if (LEAN) head_logits_ce16<true>(a, nb, l, db1p, lane, wave, la, ca, na);
+    else head_logits_ce(a, nb, l, lane, wave, la, ca, na);
     const f32x4 gh = head_dh(a, nb, l, lane, wave);
     db1acc += (gh[0] + gh[1]) + (gh[2] + gh[3]);
     if (wave < 4) {
@@ -595,7 +667,18 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
   if (fq == 0) db1p[(wave >> 2) * 64 + (wave & 3) * 16 + fr] = db1acc;
   db2acc += __shfl_xor(db2acc, 16, 64);
   db2acc += __shfl_xor(db2acc, 32, 64);
-  if (wave < 4) {
+  if (LEAN) {
+    // the metrics live on all 16 waves: each wave's sums go through LDS (behind db1p's 256 floats) and one
+    // thread adds them up in wave order, so the result does not depend on the order of atomics
+    la = rows4_sum(la);
+    ca = rows4_sum(ca);
+    na = rows4_sum(na);
+    if (lane == 0) {
+      db1p[256 + wave * 4 + 0] = la;
+      db1p[256 + wave * 4 + 1] = ca;
+      db1p[256 + wave * 4 + 2] = na;
+    }
+  } else if (wave < 4) {
     la = rows4_sum(la);
     ca = rows4_sum(ca);
     na = rows4_sum(na);
@@ -606,6 +689,20 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
     }
   }
   lds_barrier();
+  if (LEAN && a.metrics && wave == 6 && lane == 0) {
+    float ls = 0.f, cs = 0.f, ns = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      ls += db1p[256 + w * 4 + 0];
+      cs += db1p[256 + w * 4 + 1];
+      ns += db1p[256 + w * 4 + 2];
+    }
+    if (ns > 0.f) {
+      atomicAdd(a.metrics + 0, ls);
+      atomicAdd(a.metrics + 1, cs);
+      atomicAdd(a.metrics + 2, ns);
+    }
+  }
   float gv[4] = {0.f, 0.f, 0.f, 0.f};
   float* gdst[4] = {nullptr, nullptr, nullptr, nullptr};
   if (wave < 4 && fr < C) {

@@ -49,6 +49,18 @@ __device__ __forceinline__ int k8_col(int fq, int i) { return fq * 8 + 4 * ((i +
 // ... and of a 64-wide (16 k per lane group) row
 __device__ __forceinline__ int k16_col(int fq, int i) { return fq * 16 + 4 * ((i + fq) & 3); }
 
+// Image geometry of a backward form: GH x GW known at compile time (the 28 x 28 of MNIST, which is all the
+// benchmark and the reference model run: the division by Wp, the workgroup count and every image stride are
+// then constants), or <0, 0>: read from the arguments (every other shape).  The forward keeps the runtime form
+// alone: specialised, it was not faster (profiles/bwd_head/NOTES.md).
+template <int GH, int GW>
+struct Geo {
+  static constexpr bool kFixed = GH > 0;
+  template <class A> __device__ __forceinline__ static int H(const A& a) { return kFixed ? GH : a.H; }
+  template <class A> __device__ __forceinline__ static int W(const A& a) { return kFixed ? GW : a.W; }
+};
+constexpr int kGH = 28, kGW = 28;   // the specialised form
+
 // The <= XR input rows of the workgroup's FB images -> xr, in two halves: issue() the coalesced float4
 // loads (16 images x 6 rows x 32 floats = 768 float4 at most: kU per thread, one pass of 256 threads),
 // store() after the prologue's common wait (the 16-byte-aligned image stride takes whole float4 stores).
@@ -238,7 +250,15 @@ struct Bwd32Chunk {
 // into the chunk (rows past nb read row nb-1, replicas past hrep read replica hrep-1 — never an address
 // outside the buffers) and the values of the clamped lanes replaced afterwards.  NREP = replica slots
 // (0: the runtime loop of the deterministic mode, after the other loads are in flight).
-template <int NREP>
+// Fine stamp 8: the chunk's operands have landed (diagnostic runs only: the wait is inside the branch)
+__device__ __forceinline__ void stamp_landed(long long* st, const Bwd32Chunk& c) {
+  if (st) {
+    asm volatile("" ::"v"(c.hv.x), "v"(c.lab), "v"(c.ptv.x), "v"(c.xv.x), "v"((int)c.amv));
+    stamp_fine(st, 8);
+  }
+}
+
+template <int NREP, class G>
 __device__ __forceinline__ void bwd32_chunk_issue(const BwdArgs& a, int tid, int p, int py, int px, int b0, int nb,
                                                   Bwd32Chunk& c) {
   const int last = nb - 1;
@@ -254,8 +274,8 @@ __device__ __forceinline__ void bwd32_chunk_issue(const BwdArgs& a, int tid, int
   c.amv = ~0ull;
   if (tid < 256) {
     const int bl = tid >> 2, r = tid & 3;
-    const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + min(bl, last)) * a.H * a.W +
-                                                        (2 * py + r) * a.W + 2 * px);
+    const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + min(bl, last)) * G::H(a) * G::W(a) +
+                                                        (2 * py + r) * G::W(a) + 2 * px);
     const float2 u = row[0], t = row[1];
     c.xv = float4{u.x, u.y, t.x, t.y};
     const int cg = tid >> 6, bb = tid & 63;
@@ -269,9 +289,8 @@ __device__ __forceinline__ void bwd32_chunk_issue(const BwdArgs& a, int tid, int
   if (pc + 1 >= nb) c.ptv.y = 0.f;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <int MODE, class G>
+__device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned char* smem) {
   float* Gs = reinterpret_cast<float*>(smem + kG32);
   float* Gts = reinterpret_cast<float*>(smem + kGt32);
   float* W1s = reinterpret_cast<float*>(smem + kW1s32);
@@ -284,9 +303,10 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   // nothing waits for it here); MODE 1 (SGD) does not read it in the trunk workgroups
   long long t_it = 0;
   if (MODE == 2) t_it = *a.iterations;
-  const unsigned nwg = gridDim.x;   // read once, ahead of the first branch (a scalar load)
+  // workgroups of the launch: read once, ahead of the first branch (a scalar load); a constant in the fixed form
+  const unsigned nwg = G::kFixed ? ((kGH - 2) / 2) * ((kGW - 2) / 2) + 1 : gridDim.x;
   stamp(a.stamps, 0);
-  const int W = a.W;
+  const int W = G::W(a);
   int tid, lane, wave, fr, fq;
   bwd32_ids(tid, lane, wave, fr, fq);
   const float* W1 = reinterpret_cast<const float*>(a.W1);
@@ -300,7 +320,7 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
     w2v = a.W2[u2 * a.C + min(c2, a.C - 1)];
     b2v = a.b2[min(c2, a.C - 1)];
   }
-  zero_other_parity(a, tid);
+  zero_other_parity_n(a, tid, (int)nwg);
   if (blockIdx.x == nwg - 1) {
     hl.w2s[(tid >> 4) * W2S + (tid & 15)] = (tid & 15) < a.C ? w2v : 0.f;
     if (tid < 16) hl.b2s[tid] = tid < a.C ? b2v : 0.f;
@@ -332,7 +352,7 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
 
   // W1 rows of the position [32][64] f32: loaded once (independent of the image chunk), stored to LDS
   // after the first chunk's loads are issued
-  const float2 w1v = *reinterpret_cast<const float2*>(W1 + (size_t)(p * CC + (tid >> 5)) * a.ldw1 + (tid & 31) * 2);
+  const float2 w1v = *reinterpret_cast<const float2*>(W1 + (size_t)(p * CC + (tid >> 5)) * (G::kFixed ? HD : a.ldw1) + (tid & 31) * 2);
 
   for (int b0 = 0; b0 < a.B; b0 += 64) {
     const int nb = min(64, a.B - b0);
@@ -342,14 +362,15 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
     // ---- prologue: this chunk's operands, every load issued before the first wait; the replica count
     // picks the number of hpre registers (uniform switch; more than kMaxRep: the deterministic mode)
     Bwd32Chunk ck;
-    if (a.hrep > kMaxRep) bwd32_chunk_issue<0>(a, tid, p, py, px, b0, nb, ck);
+    if (a.hrep > kMaxRep) bwd32_chunk_issue<0, G>(a, tid, p, py, px, b0, nb, ck);
     else switch (a.hrep) {
-      case 1: bwd32_chunk_issue<1>(a, tid, p, py, px, b0, nb, ck); break;
-      case 2: bwd32_chunk_issue<2>(a, tid, p, py, px, b0, nb, ck); break;
-      case 3: case 4: bwd32_chunk_issue<4>(a, tid, p, py, px, b0, nb, ck); break;
-      default: bwd32_chunk_issue<8>(a, tid, p, py, px, b0, nb, ck); break;
+      case 1: bwd32_chunk_issue<1, G>(a, tid, p, py, px, b0, nb, ck); break;
+      case 2: bwd32_chunk_issue<2, G>(a, tid, p, py, px, b0, nb, ck); break;
+      case 3: case 4: bwd32_chunk_issue<4, G>(a, tid, p, py, px, b0, nb, ck); break;
+      default: bwd32_chunk_issue<8, G>(a, tid, p, py, px, b0, nb, ck); break;
     }
     stamp(a.stamps, 1);
+    stamp_landed(a.stamps, ck);
     // the selects of the clamped chunk-0 loads use this iteration's thread indices: they stay here, behind
     // the chunk's loads, and are not moved up to the loads they would wait for (has_b1: always a.b1 != null)
     const bool has_b1 = a.b1 && tid >= 0;
@@ -369,15 +390,18 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
       *reinterpret_cast<uint64_t*>(am + bb * CC + cg * 8) = ck.amv;
     }
     lds_barrier();
+    stamp_fine(a.stamps, 9);
     // ---- the head recomputed: G = dH (f32) into LDS, row-major and transposed
     {
-      float la = 0.f, ca = 0.f, na = 0.f;   // the head workgroup keeps these
-      head_logits_ce(a, nb, hl, lane, wave, la, ca, na);
+      float la = 0.f, ca = 0.f, na = 0.f;   // the head workgroup keeps these: not computed here
+      head_logits_ce16<false>(a, nb, hl, Gs, lane, wave, la, ca, na);   // partial 0 in Gs, free until dH
+      stamp_fine(a.stamps, 11);
       const f32x4 gh = head_dh(a, nb, hl, lane, wave);
       const int rt = wave >> 2, j = (wave & 3) * 16 + fr;
 #pragma unroll
       for (int i = 0; i < 4; ++i) Gs[(rt * 16 + fq * 4 + i) * GS32 + j] = gh[i];
       *reinterpret_cast<float4*>(Gts + j * GS32 + rt * 16 + fq * 4) = float4{gh[0], gh[1], gh[2], gh[3]};
+      stamp_fine(a.stamps, 12);
     }
     lds_barrier();
     stamp(a.stamps, 2);
@@ -468,10 +492,33 @@ __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   stamp(a.stamps, 5);
 }
 
+// The runtime-geometry form (the fallback for every shape but 28 x 28) and the specialised one
+template <int MODE>
+__global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  convnet32_bwd_body<MODE, Geo<0, 0>>(a, smem);
+}
+template <int MODE>
+__global__ __launch_bounds__(1024) void convnet32g_bwd_kernel(BwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  convnet32_bwd_body<MODE, Geo<kGH, kGW>>(a, smem);
+}
+
 }  // namespace tde
 
 using namespace tde;
 using namespace tde::cnet;
+
+// The form the backward's entry point launches: the specialised kernels for 28 x 28 images, the runtime-geometry
+// ones for every other shape.  tde_convnet_f32_runtime_geom(1) forces the runtime form for every shape (the tests
+// compare the two forms on the same inputs); it returns the previous setting.
+static int g_runtime_geom = 0;
+static bool geom_fixed(int H, int W) { return !g_runtime_geom && H == kGH && W == kGW; }
+TDE_API int tde_convnet_f32_runtime_geom(int on) {
+  const int prev = g_runtime_geom;
+  g_runtime_geom = on ? 1 : 0;
+  return prev;
+}
 
 // Float32 forward: W1 is the f32 master Dense(64) kernel [K][64] (ldw1 = 64), Pt f32 [K][ldPt].
 // opt / off_wc / off_bc / inc_iter / hrep as tde_convnet_fwd.
@@ -525,12 +572,22 @@ TDE_API int tde_convnet_bwd_f32(const float* x, const void* amax, int lda, const
     (void)hipFuncSetAttribute((const void*)convnet32_bwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
     (void)hipFuncSetAttribute((const void*)convnet32_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
     (void)hipFuncSetAttribute((const void*)convnet32_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
+    (void)hipFuncSetAttribute((const void*)convnet32g_bwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
+    (void)hipFuncSetAttribute((const void*)convnet32g_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
+    (void)hipFuncSetAttribute((const void*)convnet32g_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
     attr_set = true;
   }
   const dim3 grid(P + 1);   // one workgroup per pooled position + the head workgroup
-  if (!opt) convnet32_bwd_kernel<0><<<grid, 1024, kBwd32Lds, stream>>>(a);
-  else if (opt->h.kind == kOptSGD) convnet32_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
-  else convnet32_bwd_kernel<2><<<grid, 1024, kBwd32Lds, stream>>>(a);
+  const int mode = !opt ? 0 : (opt->h.kind == kOptSGD ? 1 : 2);
+  if (geom_fixed(H, W)) {
+    if (mode == 0) convnet32g_bwd_kernel<0><<<grid, 1024, kBwd32Lds, stream>>>(a);
+    else if (mode == 1) convnet32g_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
+    else convnet32g_bwd_kernel<2><<<grid, 1024, kBwd32Lds, stream>>>(a);
+  } else {
+    if (mode == 0) convnet32_bwd_kernel<0><<<grid, 1024, kBwd32Lds, stream>>>(a);
+    else if (mode == 1) convnet32_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
+    else convnet32_bwd_kernel<2><<<grid, 1024, kBwd32Lds, stream>>>(a);
+  }
   TDE_LAUNCH_CHECK();
   return 0;
 }
