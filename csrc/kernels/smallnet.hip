@@ -31,6 +31,7 @@
 
 #include "tde_common.h"
 #include "tde_loss.h"
+#include "tde_metric.h"
 #include "tde_optim.h"
 #include "tde_philox.h"
 #include "tde_sched.h"
@@ -86,6 +87,13 @@ struct SnArgs {
 // kernarg layout and its program.
 struct SnLossArgs : SnArgs {
   LossSpec ls;
+};
+// ... of the two metric kernels (smallnet_step_metric_kernel, smallnet_step_loss_metric_kernel): the plan's second
+// accumulator and its spec appended (top-k hits, crossentropy sums, confusion block; tde_metric.h).  `ls` is read
+// by the second of them only.
+struct SnMetricArgs : SnLossArgs {
+  MetricSpec ms;
+  float* ext;
 };
 
 // The step kernel holds its per-image program twice (sn_step<NL>, chosen per launch): NL = false knows
@@ -924,7 +932,8 @@ __device__ __forceinline__ void sn_by_cg(int Co, F&& f) {
 }
 
 // LOSS (with Args = SnLossArgs): the one-wave loss block follows a.ls; everything else is the same program.
-template <bool NL, bool LOSS = false, class Args = SnArgs>
+// METRIC (with Args = SnMetricArgs): the loss block also adds the row's words to a.ext, train and eval mode.
+template <bool NL, bool LOSS = false, bool METRIC = false, class Args = SnArgs>
 __device__ __forceinline__ void sn_step(const Args& a, float* s) {
   const int b = blockIdx.x;
   const bool train = a.mode == 0;
@@ -1006,11 +1015,12 @@ __device__ __forceinline__ void sn_step(const Args& a, float* s) {
     float se = 0.f, sl = 0.f;
     for (int c = lane; c < C; c += 64) {
       se += __expf(lg[c] - mx);
-      if constexpr (LOSS) sl += lg[c];
+      if constexpr (LOSS || METRIC) sl += lg[c];
     }
     se = wave_sum(se);
     const int y = a.y ? a.y[b] : 0;
     const float ly = (y >= 0 && y < C) ? lg[y] : mx;
+    if constexpr (!LOSS && METRIC) sl = wave_sum(sl);
     float loss, w = 1.f;
     if constexpr (LOSS) {
       sl = wave_sum(sl);
@@ -1022,6 +1032,23 @@ __device__ __forceinline__ void sn_step(const Args& a, float* s) {
     }
     const float corr = am == y ? 1.f : 0.f;
     const float inv = 1.f / se;
+    if constexpr (METRIC) {
+      // the row's words of the second accumulator, while the logits are still in place (modes 0 and 1)
+      if (a.mode != 2 && a.ext) {
+        const bool valid = y >= 0 && y < C;
+        const float rank = a.ms.n_topk > 0 ? metric_rank(lg, C, ly, lane) : 0.f;
+        if (lane == 0) {
+          const float lse = mx + __logf(se);
+#pragma unroll
+          for (int i = 0; i < kMetricTopK; ++i)
+            if (i < a.ms.n_topk) atomicAdd(&a.ext[a.ms.off_topk + i], metric_topk_hit(valid, ly, rank, a.ms.k[i]));
+#pragma unroll
+          for (int i = 0; i < kMetricCe; ++i)
+            if (i < a.ms.n_ce) atomicAdd(&a.ext[a.ms.off_ce + i], metric_ce_row(a.ms.smooth[i], lse, ly, sl, C));
+          if (a.ms.cm) metric_cm_add(a.ext, a.ms, y, am, C);
+        }
+      }
+    }
     // every lane has read lg[y] above before any lane overwrites the logits below
     __builtin_amdgcn_wave_barrier();
     for (int c = lane; c < C; c += 64) {
@@ -1081,8 +1108,20 @@ __global__ __launch_bounds__(kSnThreads) void smallnet_step_kernel(SnArgs a) {
 
 __global__ __launch_bounds__(kSnThreads) void smallnet_step_loss_kernel(SnLossArgs a) {
   __shared__ __attribute__((aligned(16))) float s[kSnLds];
-  if (a.nonlinear) sn_step<true, true>(a, s);
-  else sn_step<false, true>(a, s);
+  if (a.nonlinear) sn_step<true, true, false, SnLossArgs>(a, s);
+  else sn_step<false, true, false, SnLossArgs>(a, s);
+}
+
+__global__ __launch_bounds__(kSnThreads) void smallnet_step_metric_kernel(SnMetricArgs a) {
+  __shared__ __attribute__((aligned(16))) float s[kSnLds];
+  if (a.nonlinear) sn_step<true, false, true, SnMetricArgs>(a, s);
+  else sn_step<false, false, true, SnMetricArgs>(a, s);
+}
+
+__global__ __launch_bounds__(kSnThreads) void smallnet_step_loss_metric_kernel(SnMetricArgs a) {
+  __shared__ __attribute__((aligned(16))) float s[kSnLds];
+  if (a.nonlinear) sn_step<true, true, true, SnMetricArgs>(a, s);
+  else sn_step<false, true, true, SnMetricArgs>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1274,7 +1313,7 @@ static int sn_step_launch(const int* layers, int nl, int mode, int B, const floa
                           int in0, int n_in0, const int* img, const int* y, float* part, int npart, float* rec,
                           int nrec, float* metrics, long long* iterations, const long long* step, float scale,
                           float* probs, int probs_softmax, long long* stamps, const LossSpec* ls,
-                          hipStream_t stream) {
+                          hipStream_t stream, const MetricSpec* ms = nullptr, float* ext = nullptr) {
   if (nl < 1 || nl > kSnMaxLayers || B <= 0) return -1;
   if (mode == 0 && (!part || !rec || !iterations || nrec < 2)) return -2;
   SnArgs a{};
@@ -1333,7 +1372,16 @@ static int sn_step_launch(const int* layers, int nl, int mode, int B, const floa
     return e ? atoi(e) : 3;
   }();
   a.mfma = mfma;
-  if (ls) {
+  if (ms) {  // the metric variants: with the loss head's spec, or the plain loss
+    if (!ext || !metric_spec_ok(*ms, a.L[nl - 1].Co)) return -10;
+    SnMetricArgs ma{};
+    static_cast<SnArgs&>(ma) = a;
+    if (ls) ma.ls = *ls;
+    ma.ms = *ms;
+    ma.ext = ext;
+    if (ls) smallnet_step_loss_metric_kernel<<<B, kSnThreads, 0, stream>>>(ma);
+    else smallnet_step_metric_kernel<<<B, kSnThreads, 0, stream>>>(ma);
+  } else if (ls) {
     SnLossArgs la{};
     static_cast<SnArgs&>(la) = a;
     la.ls = *ls;
@@ -1367,6 +1415,24 @@ TDE_API int tde_smallnet_step_loss(const int* layers, int nl, int mode, int B, c
   if (!loss_spec_ok(ls)) return -9;
   return sn_step_launch(layers, nl, mode, B, w, x, x_stride, in0, n_in0, img, y, part, npart, rec, nrec, metrics,
                         iterations, step, scale, probs, probs_softmax, stamps, &ls, stream);
+}
+
+// The step that also feeds the plan's second metric accumulator (smallnet_step_metric_kernel, or
+// smallnet_step_loss_metric_kernel with has_loss: smooth / class_w as for tde_smallnet_step_loss): spec is a
+// MetricSpec laid out for the head's classes, ext its spec->words floats.  A bad metric spec returns -10.
+TDE_API int tde_smallnet_step_metric(const int* layers, int nl, int mode, int B, const float* w, const float* x,
+                                     int x_stride, int in0, int n_in0, const int* img, const int* y, float* part,
+                                     int npart, float* rec, int nrec, float* metrics, long long* iterations,
+                                     const long long* step, float scale, float* probs, int probs_softmax,
+                                     long long* stamps, int has_loss, float smooth, const float* class_w,
+                                     const void* spec, float* ext, hipStream_t stream) {
+  const LossSpec ls{smooth, class_w != nullptr, class_w};
+  if (has_loss && !loss_spec_ok(ls)) return -9;
+  if (!spec || !ext) return -10;
+  const MetricSpec ms = *(const MetricSpec*)spec;
+  return sn_step_launch(layers, nl, mode, B, w, x, x_stride, in0, n_in0, img, y, part, npart, rec, nrec, metrics,
+                        iterations, step, scale, probs, probs_softmax, stamps, has_loss ? &ls : nullptr, stream, &ms,
+                        ext);
 }
 
 // ranges: nr x {part_lo, n, flat_off}; dense: nd x {In, Co, xo, go, w_off, b_off, blk0, nblk}.

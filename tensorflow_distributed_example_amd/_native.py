@@ -127,6 +127,11 @@ _HIP_PROTOS = {
                                 p, p]),
     "tde_smallnet_step_loss": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p,
                                      i32, p, f32, p, p]),
+    "tde_smallnet_step_metric": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p,
+                                       i32, p, i32, f32, p, p, p, p]),
+    # top-k / crossentropy / confusion counts of a batch of logits (csrc/kernels/metrichead.hip)
+    "tde_metric_rows": (i32, [p, i64, p, i32, i32, p, p, p]),
+    "tde_metric_abi": (i32, [p, i32]),
     # softmax-CE with label smoothing / class weights (csrc/kernels/losshead.hip)
     "tde_xent_spec": (i32, [p, i64, p, i32, i32, f32, p, i64, i32, p, p, i32, p, f32, p, p]),
     "tde_smallnet_wgrad": (i32, [p, i32, p, i32, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p, i32, i32, f32, f32,

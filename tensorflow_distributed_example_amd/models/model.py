@@ -233,6 +233,9 @@ class Model:
                                       "feed; metrics= are unweighted, as fit(class_weight=) leaves them")
         self.compiled_metrics = list(metrics or [])
         self._metric_names = MT.resolve(metrics, self.loss)
+        MT.check_head(self._metric_names, self)
+        # the metrics beyond the accuracy: where each lives in the plans' second accumulator
+        self._metric_names.layout = MT.metric_spec(self._metric_names, self.loss, self.output_shape[-1])
         if steps_per_execution is not None:
             self.steps_per_execution = int(steps_per_execution)
         if DS.has_strategy():

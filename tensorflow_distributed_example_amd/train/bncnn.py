@@ -157,6 +157,13 @@ def match_bncnn(model, loss):
         warnings.warn(f"model {model.name!r}: the fused BN-CNN step has no loss head for {LS.spec_reason(loss)}; "
                       "running the per-layer kernel plan")
         return None
+    from .program import extra_metrics
+    extra = extra_metrics(model)
+    if extra:
+        import warnings
+        warnings.warn(f"model {model.name!r}: the fused BN-CNN step has no metric head for {extra}; running the "
+                      "per-layer kernel plan")
+        return None
     return dict(convs=convs, dense=(d, bn_d, drop), head=head)
 
 

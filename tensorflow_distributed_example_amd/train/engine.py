@@ -235,7 +235,7 @@ def evaluate(model, x=None, y=None, batch_size=None, verbose="auto", steps=None,
         print(" - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
     if return_dict:
         return logs
-    return [logs["loss"]] + ([logs["accuracy"]] if "accuracy" in logs else [])
+    return [logs["loss"]] + [v for k, v in logs.items() if k != "loss"]   # the metrics in compile order
 
 
 def predict(model, x, batch_size=None, verbose=0, steps=None):

@@ -938,9 +938,11 @@ class _Head(_Stage):
         self.H = tin.shape[0]
         self.W = st.view(self.wname)
         self.f32 = plan.f32
-        # a non-trivial loss spec takes the general path, with the spec kernel in place of xent
+        # a non-trivial loss spec takes the general path, with the spec kernel in place of xent; metrics beyond
+        # the accuracy take it too: their launch reads the logits buffer
         self.fused = (not self.f32 and not plan.det and self.C <= 16 and self.H <= 256 and self.H % 4 == 0
-                      and not plan.loss_spec and os.environ.get("TDE_FUSED_HEAD", "1") != "0")
+                      and not plan.loss_spec and not plan.metric_spec
+                      and os.environ.get("TDE_FUSED_HEAD", "1") != "0")
         self.shadows = {} if (self.fused or self.f32) else {self.wname: ("row", "col") if self.need_dgrad else ("col",)}
         self.pre = None   # absorbed Dense: its ReLU mask and bias gradient are applied by the head launch
 
@@ -998,6 +1000,13 @@ class _Head(_Stage):
                          probs_are_logits=self.logits_out, bf16=not self.f32)
 
     def fwd(self, p, B, training, mode="train"):
+        self._fwd(p, B, mode)
+        if p.metric_layout is not None and mode != "predict":
+            # right behind the softmax-CE launch, on its stream: the extra metrics of the same logits
+            from ..ops import metric_ops as OM
+            OM.metric_rows(self.logits, p._labels, B, self.C, p.metric_spec, p.metrics_ext)
+
+    def _fwd(self, p, B, mode):
         if self.fused:
             self._fused_fwd(p, B, mode)
             return

@@ -73,6 +73,17 @@ class ReplicaPlan:
         # fit(class_weight=) -- the table of row weights by class, which ``set_class_weight`` rewrites in place
         self.smooth = 0.0
         self.class_w = None
+        # metrics beyond the accuracy (metrics.py): their layout, the ctypes MetricSpec of the launches and the
+        # second accumulator the layout describes; None for a model compiled without them
+        self.metric_layout = getattr(getattr(model, "_metric_names", None), "layout", None)
+        self.metrics_ext = None
+        if self.metric_layout is not None:
+            self.metrics_ext = torch.zeros(self.metric_layout.words, dtype=torch.float32, device=self.device)
+
+    @property
+    def metric_spec(self):
+        """The ``MetricSpec`` (csrc/include/tde_metric.h) of a plan built for extra metrics, else None."""
+        return self.metric_layout.struct() if self.metric_layout is not None else None
 
     def _init_loss_spec(self, loss, classes):
         """Take the spec of ``loss`` (a plan that runs a non-trivial one calls this from its constructor)."""
@@ -98,6 +109,12 @@ class ReplicaPlan:
 
     def reset_metrics(self):
         self.metrics.zero_()
+        if self.metrics_ext is not None:
+            self.metrics_ext.zero_()
+
+    def all_metrics(self):
+        """``metrics`` with ``metrics_ext`` behind it: what ``metrics.logs_from`` reads."""
+        return self.metrics if self.metrics_ext is None else torch.cat([self.metrics, self.metrics_ext])
 
     def set_iterations(self, step):
         """Assign the device step counter from the host (checkpoint restore)."""
@@ -304,6 +321,31 @@ class ReferencePlan(ReplicaPlan):
             loss_sum = loss_sum + float(ls.shape[0]) * RG.penalty(self.store.w.detach(), self.reg_segs).float()
         self.metrics += torch.stack([loss_sum, correct, torch.tensor(float(ls.shape[0]), device=out.device),
                                      torch.zeros((), device=out.device)])
+        if self.metric_layout is not None:
+            self._acc_ext(out, yy)
+
+    def _acc_ext(self, out, yy):
+        """The words of ``metrics_ext`` with torch (the layout of csrc/include/tde_metric.h)."""
+        from .. import losses as LS
+        lay, ext = self.metric_layout, self.metrics_ext
+        z = out.detach().float()
+        if getattr(self.model.layers[-1], "activation", None) == "softmax" and not self.strip_softmax:
+            z = z.clamp_min(torch.finfo(torch.float32).tiny).log()   # probabilities: log p is the logits up to lse
+        C = z.shape[1]
+        valid = (yy >= 0) & (yy < C)
+        yc = yy.clamp(0, C - 1)
+        zy = torch.where(valid, z.gather(1, yc[:, None]).squeeze(1), z.max(dim=1).values)
+        if lay.k:
+            rank = (z > zy[:, None]).sum(dim=1)
+            for i, k in enumerate(lay.k):
+                ext[lay.off_topk + i] += ((rank < k) & torch.isfinite(zy) & valid).sum().float()
+        for i, e in enumerate(lay.smooth):
+            ext[lay.off_ce + i] += LS.softmax_ce(z, yy, e).sum().float()
+        if lay.cm:
+            am = z.argmax(dim=1)[valid]
+            cm = ext[lay.off_cm: lay.off_cm + C * C].view(C, C)
+            cm.index_put_((yy[valid], am), torch.ones(am.shape[0], dtype=torch.float32, device=z.device),
+                          accumulate=True)
 
     def add_eval_penalty(self, rows):
         """``_acc`` has added it already."""
@@ -547,6 +589,13 @@ class OptimizerKernel:
         N.check(rc, "tde_optim_apply")
 
 
+def extra_metrics(model):
+    """The names of the model's compiled metrics beyond the accuracy ("" without any), for a plan's warning that
+    it declines them."""
+    lay = getattr(getattr(model, "_metric_names", None), "layout", None)
+    return lay.describe() if lay is not None else ""
+
+
 def match_convnet(model, loss):
     """Pattern of the DWK/TF2M small CNN: Conv2D(3x3,relu,bias) on 1 channel ·
     MaxPooling2D(2) · Flatten · Dense(bias[,relu]) · Dense(bias[,softmax]) + softmax-CE with a trivial spec
@@ -573,6 +622,12 @@ def match_convnet(model, loss):
         import warnings
         warnings.warn(f"model {model.name!r}: the fused small-CNN step has no loss head for "
                       f"{LS.spec_reason(loss)}; running the per-layer kernel plan")
+        return None
+    extra = extra_metrics(model)
+    if extra:
+        import warnings
+        warnings.warn(f"model {model.name!r}: the fused small-CNN step has no metric head for {extra}; running "
+                      "the per-layer kernel plan")
         return None
     force_gen = os.environ.get("TDE_CONVNET_GENERIC", "0") == "1"   # A/B: the generic kernels at any width
     if c.filters != 32 or d1.units != 64 or force_gen:

@@ -658,7 +658,7 @@ class Program:
     def local_metrics(self):
         acc = None
         for p in self.plans:
-            m = p.metrics.detach().double().cpu()
+            m = p.all_metrics().detach().double().cpu()
             acc = m if acc is None else acc + m
         return acc
 
@@ -667,7 +667,7 @@ class Program:
         if self.comm is None:
             return self.local_metrics()
         self.comm.check_health()   # surfaces a timed-out peer wait of the xGMI all-reduce
-        bufs = [p.metrics.clone() for p in self.plans]
+        bufs = [p.all_metrics().clone() for p in self.plans]   # both accumulators in one all-reduce
         self.comm.all_reduce_(bufs)
         for d in self.devices:
             if d.type == "cuda":

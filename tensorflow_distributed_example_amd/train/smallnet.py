@@ -305,6 +305,14 @@ class SmallNetPlan(ReplicaPlan):
                 self.rec.data_ptr() if train else None, self.nrec, self.metrics.data_ptr(),
                 self.iterations.data_ptr(), N.ptr(self.step_word), float(self.scale), N.ptr(probs),
                 self.probs_softmax, N.ptr(self.stamps))
+        if self.metric_layout is not None and mode != 2:
+            # the metric variants (with or without the loss head's spec) also feed metrics_ext
+            rc = self.lib.tde_smallnet_step_metric(*args, int(self.loss_spec), float(self.smooth),
+                                                   N.ptr(self.class_w) if train else None,
+                                                   ctypes.byref(self.metric_spec), self.metrics_ext.data_ptr(),
+                                                   N.stream_ptr())
+            N.check(rc, "tde_smallnet_step_metric")
+            return
         if self.loss_spec:
             # the weights apply to the training loss and gradient only
             rc = self.lib.tde_smallnet_step_loss(*args, float(self.smooth), N.ptr(self.class_w) if train else None,
