@@ -122,6 +122,9 @@ _HIP_PROTOS = {
     "tde_stem_pack": (i32, [p, p, p, p, p, p]),
     "tde_gather_rows_dev": (i32, [p, i64, i64, p, i64, p, p, p]),
     "tde_copy_pairs": (i32, [i32, p, p, p, p]),
+    # the input stage inside the ring-filling launch (csrc/kernels/augment.hip)
+    "tde_stage_rows_aug": (i32, [p, i32, i64, p, i64, i32, i32, i32, i32, p, p, i64, p, p, p]),
+    "tde_augment_abi": (i32, [p, i32]),
     "tde_smallnet_limits": (i32, [p]),
     "tde_smallnet_step": (i32, [p, i32, i32, i32, p, p, i32, i32, i32, p, p, p, i32, p, i32, p, p, p, f32, p, i32,
                                 p, p]),

@@ -167,7 +167,8 @@ def build(model, values: dict, slots: dict | None = None, iterations: int | None
             nodes[vn]["attrs"].append(("VARIABLE_VALUE", s.full_name, key))
             out[key] = np.asarray(values[s.full_name])
             var_node[s.full_name] = (vn, f"layer_with_weights-{i}/{s.name}")
-    for j, layer in enumerate(model.layers):   # every layer is also reachable as layer-<j>
+    # every layer is also reachable as layer-<j> (the input stage holds no state and is left out)
+    for j, layer in enumerate(getattr(model, "body_layers", model.layers)):
         ln = layer_node.get(id(layer))
         if ln is None:
             ln = new_node()

@@ -536,9 +536,102 @@ class Add(Layer):
         return out
 
 
+class InputStageLayer(Layer):
+    """A random image transform of the model's input stage: the unbroken chain of such layers directly behind
+    the model input.  No weights, shape preserved, the identity whenever the learning phase is not training.
+    No plan runs these layers: the launch that fills the training program's input ring applies them
+    (``csrc/kernels/augment.hip``; host twin ``ops/augment.py``), as a pure function of (seed, global step,
+    index in the stage, local row), and the plans see the model without them (``Model._nodes``)."""
+    _seed_base = 104729   # make_generator(_seed_base + j) draws the seed of a layer built without one
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise ValueError(f"{self.name}: expects channels_last images (H, W, C), got shape {tuple(s)}")
+        return tuple(s)
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        return x   # the direct call runs inference ops
+
+    def resolved_seed(self, j):
+        """The Philox key of this layer at index ``j`` of the input stage."""
+        if self.seed is not None:
+            return int(self.seed)
+        g = K.make_generator(self._seed_base + j)
+        return int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
+
+
+class RandomFlip(InputStageLayer):
+    _prefix = "random_flip"
+    MODES = ("horizontal", "vertical", "horizontal_and_vertical")
+
+    def __init__(self, mode="horizontal_and_vertical", seed=None, **kw):
+        super().__init__(**kw)
+        if mode not in self.MODES:
+            raise ValueError(f"RandomFlip: mode must be one of {self.MODES}, got {mode!r}")
+        self.mode = mode
+        self.seed = None if seed is None else int(seed)
+
+    def aug_layer(self, j):
+        from ..ops import augment as AU
+        return AU.flip_layer(self.mode, j, self.resolved_seed(j))
+
+    def get_config(self):
+        return dict(name=self.name, mode=self.mode, seed=self.seed)
+
+
+def _translation_factor(v, what):
+    """A factor f >= 0 (the range [-f, f]) or a pair (lo, hi) with -1 <= lo <= hi <= 1 -> (lo, hi)."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"RandomTranslation: {what} must be a float or a (lo, hi) pair, got {v!r}")
+        lo, hi = float(v[0]), float(v[1])
+    elif isinstance(v, (int, float)) and not isinstance(v, bool):
+        if v < 0:
+            raise ValueError(f"RandomTranslation: {what} must not be negative, got {v!r}")
+        lo, hi = -float(v), float(v)
+    else:
+        raise ValueError(f"RandomTranslation: {what} must be a float or a (lo, hi) pair, got {v!r}")
+    if not (-1.0 <= lo <= hi <= 1.0):
+        raise ValueError(f"RandomTranslation: {what} needs -1 <= lo <= hi <= 1, got {v!r}")
+    return lo, hi
+
+
+class RandomTranslation(InputStageLayer):
+    _prefix = "random_translation"
+    FILL_MODES = ("constant", "nearest", "reflect", "wrap")
+    INTERPOLATIONS = ("nearest", "bilinear")
+
+    def __init__(self, height_factor, width_factor, fill_mode="reflect", interpolation="bilinear", seed=None,
+                 fill_value=0.0, **kw):
+        super().__init__(**kw)
+        self.height_factor = tuple(height_factor) if isinstance(height_factor, (tuple, list)) else height_factor
+        self.width_factor = tuple(width_factor) if isinstance(width_factor, (tuple, list)) else width_factor
+        self.height_range = _translation_factor(height_factor, "height_factor")
+        self.width_range = _translation_factor(width_factor, "width_factor")
+        if fill_mode not in self.FILL_MODES:
+            raise ValueError(f"RandomTranslation: fill_mode must be one of {self.FILL_MODES}, got {fill_mode!r}")
+        if interpolation not in self.INTERPOLATIONS:
+            raise ValueError(f"RandomTranslation: interpolation must be one of {self.INTERPOLATIONS}, "
+                             f"got {interpolation!r}")
+        self.fill_mode = fill_mode
+        self.interpolation = interpolation
+        self.seed = None if seed is None else int(seed)
+        self.fill_value = float(fill_value)
+
+    def aug_layer(self, j):
+        from ..ops import augment as AU
+        return AU.translate_layer(self.height_range, self.width_range, self.fill_mode, self.interpolation,
+                                  self.fill_value, j, self.resolved_seed(j))
+
+    def get_config(self):
+        return dict(name=self.name, height_factor=self.height_factor, width_factor=self.width_factor,
+                    fill_mode=self.fill_mode, interpolation=self.interpolation, seed=self.seed,
+                    fill_value=self.fill_value)
+
+
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
-                                         Dropout, BatchNormalization, Add]}
+                                         Dropout, BatchNormalization, Add, RandomFlip, RandomTranslation]}
 
 
 def from_config(cls_name, cfg):

@@ -56,10 +56,78 @@ class Model:
     def built(self):
         return self._store is not None
 
-    def _nodes(self):
+    def _all_nodes(self):
         """Execution graph: [(layer, input tensor ids, output tensor id)] in topological order;
         tensor 0 is the model input, the last node's output is the model output."""
         raise NotImplementedError
+
+    def _split_input_stage(self):
+        """(input-stage layers, body nodes).  The input stage is the unbroken chain of ``InputStageLayer``s
+        directly behind the model input, each the only consumer of its input; the body is the rest of the
+        graph with the stage's output as tensor 0 and the other tensors renumbered in order."""
+        nodes = self._all_nodes()
+        # cached per node list (Sequential.add makes a new one); a model without such layers is its own body
+        key = tuple(id(l) for l, _, _ in nodes)
+        cached = getattr(self, "_stage_split", None)
+        if cached is not None and cached[0] == key:
+            return list(cached[1]), list(cached[2])
+        stage, body = self._compute_input_stage(nodes)
+        self._stage_split = (key, stage, body)
+        return list(stage), list(body)
+
+    @staticmethod
+    def _compute_input_stage(nodes):
+        if not any(isinstance(l, L.InputStageLayer) for l, _, _ in nodes):
+            return [], nodes
+        stage, cur, skip = [], 0, set()
+        while True:
+            cons = [i for i, (_, ins, _) in enumerate(nodes) if cur in ins]
+            if len(cons) != 1 or not isinstance(nodes[cons[0]][0], L.InputStageLayer):
+                break
+            stage.append(nodes[cons[0]][0])
+            skip.add(cons[0])
+            cur = nodes[cons[0]][2]
+        if not stage:
+            return stage, nodes
+        ids = {cur: 0}
+        body = []
+        for i, (layer, ins, out) in enumerate(nodes):
+            if i in skip:
+                continue
+            ids[out] = len(ids)
+            body.append((layer, [ids[j] for j in ins], ids[out]))
+        return stage, body
+
+    def _nodes(self):
+        """The graph every plan, matcher and exporter sees: ``_all_nodes`` without the input stage (the
+        launch that fills the input ring applies it; it is the identity outside training)."""
+        return self._split_input_stage()[1]
+
+    @property
+    def input_stage(self):
+        """The RandomFlip / RandomTranslation layers in front of the model, in model order."""
+        return self._split_input_stage()[0]
+
+    @property
+    def body_layers(self):
+        """``layers`` without the input stage."""
+        stage = set(map(id, self.input_stage))
+        return [l for l in self.layers if id(l) not in stage]
+
+    def _check_input_stage(self):
+        """compile(): the random image layers stand in the input stage only, and it is one the staging
+        launch can run."""
+        from ..ops import augment as AU
+        stage, body = self._split_input_stage()
+        for layer, _, _ in body:
+            if isinstance(layer, L.InputStageLayer):
+                raise ValueError(f"layer {layer.name!r} ({type(layer).__name__}) may only stand in the model's "
+                                 "input stage: the unbroken chain of RandomFlip / RandomTranslation layers "
+                                 "directly behind the model input")
+        if stage:
+            if not body:
+                raise ValueError(f"model {self.name!r} has nothing behind its input stage")
+            AU.stage_spec(stage)   # raises on more layers than the launch takes
 
     def _create_store(self):
         st = DS.get_strategy()
@@ -226,6 +294,7 @@ class Model:
     def compile(self, optimizer="rmsprop", loss=None, metrics=None, loss_weights=None, weighted_metrics=None,
                 run_eagerly=None, steps_per_execution=None, jit_compile=None, **kw):
         self._require_built()
+        self._check_input_stage()
         self.optimizer = OP.get(optimizer)
         self.loss = LS.get(loss)
         if weighted_metrics:
@@ -290,7 +359,7 @@ class Sequential(Model):
     def layers(self):
         return [l for l in self._layers if not isinstance(l, L.InputLayer)]
 
-    def _nodes(self):
+    def _all_nodes(self):
         return [(l, [i], i + 1) for i, l in enumerate(self.layers)]
 
     def add(self, layer):
@@ -447,7 +516,7 @@ class Functional(Model):
     def layers(self):
         return [l for l, _, _ in self._graph]
 
-    def _nodes(self):
+    def _all_nodes(self):
         return list(self._graph)
 
     def build(self, input_shape=None):

@@ -97,6 +97,25 @@ def mnist_mlp(name=None):
     ], name=name)
 
 
+def with_input_stage(model, stage, name=None):
+    """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
+    ``stage``: a list of RandomFlip / RandomTranslation layers.  The input becomes the image itself: a model
+    that starts by reshaping flat rows (``mnist_bn_cnn``) takes its Reshape target as the input shape.  The
+    layers of ``stage`` become the new model's own (the first one is given the model's input shape): pass
+    fresh layers, not ones that stand in another model."""
+    cfg = model.get_config()
+    first = model._layers[0]
+    shape = tuple(first.target_shape) if isinstance(first, L.Reshape) else tuple(cfg["input_shape"])
+    out = Sequential(name=name)
+    for i, layer in enumerate(stage):
+        if i == 0:
+            layer.input_shape_arg = shape
+        out.add(layer)
+    for lc in cfg["layers"]:
+        out.add(L.from_config(lc["class_name"], lc["config"]))
+    return out
+
+
 def _l2(l2):
     """kernel_regularizer of the ResNets' conv and dense kernels: ``l2=None`` builds the unregularized model."""
     from .. import regularizers

@@ -125,8 +125,10 @@ class DeviceFeed:
                 for i in per_replica_idx]
 
     # ------------------------------------------------------------------ device staging
-    def stage(self, group):
-        """group: S global batches, each a list of per-replica index arrays of exactly B rows."""
+    def stage(self, group, step0=0):
+        """group: S global batches, each a list of per-replica index arrays of exactly B rows; ``step0``: the
+        global step of the first of them.  A program with an input stage gets its x rows through
+        ``tde_stage_rows_aug`` (csrc/kernels/augment.hip) in place of the gather: the same launch count."""
         prog = self.prog
         S, B = prog.S, prog.B
         for r, d in enumerate(prog.devices):
@@ -147,10 +149,14 @@ class DeviceFeed:
                 st["k"] ^= 1
                 sp = self.N.stream_ptr()
                 xr, yr = prog.x_ring[r], prog.y_ring[r]
-                rc = self.lib.tde_gather_rows_dev(st["x"].data_ptr(), self.per * st["x"].element_size(), self.n,
-                                                  st["idx"].data_ptr(), S * B, xr.data_ptr(), st["bad"].data_ptr(),
-                                                  sp)
-                self.N.check(rc, "tde_gather_rows_dev (x)")
+                if prog.aug is not None:
+                    from ..ops import augment as AU
+                    AU.stage_rows(st["x"], self.n, st["idx"], S * B, B, prog.x_shape, xr, prog.aug, step0, st["bad"])
+                else:
+                    rc = self.lib.tde_gather_rows_dev(st["x"].data_ptr(), self.per * st["x"].element_size(), self.n,
+                                                      st["idx"].data_ptr(), S * B, xr.data_ptr(),
+                                                      st["bad"].data_ptr(), sp)
+                    self.N.check(rc, "tde_gather_rows_dev (x)")
                 rc = self.lib.tde_gather_rows_dev(st["y"].data_ptr(), 4, self.n, st["idx"].data_ptr(), S * B,
                                                   yr.data_ptr(), st["bad"].data_ptr(), sp)
                 self.N.check(rc, "tde_gather_rows_dev (y)")

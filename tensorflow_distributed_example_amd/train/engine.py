@@ -154,18 +154,19 @@ def fit(model, x=None, y=None, batch_size=None, epochs=1, verbose="auto", callba
             else:
                 full = [all(len(r[1]) == prog.B for r in g) for g in group]
             cl.on_train_batch_begin(step)
+            step0 = model.optimizer.iterations + step   # the global step of the group's first batch (host mirror)
             if len(group) == S and all(full):
                 if feed is not None:
-                    feed.stage(group)
+                    feed.stage(group, step0)
                 else:
-                    prog.stage(_stack_steps(group))
+                    prog.stage(_stack_steps(group), step0)
                 prog.run()
             else:
-                for g in group:
+                for k, g in enumerate(group):
                     if feed is not None:
                         g = feed.host_batch(g)
                     glob = sum(len(r[1]) for r in g) * strategy.num_workers
-                    prog.run_single(g, glob)
+                    prog.run_single(g, glob, step0 + k)
             step += len(group)
             n_exec += 1
             if check_every and n_exec % check_every == 0:

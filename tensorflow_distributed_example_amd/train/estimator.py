@@ -254,6 +254,16 @@ class Estimator:
         if max_steps is not None:
             max_steps = int(math.ceil(max_steps))
         st = self._train_strategy()
+        stage = getattr(self.model, "input_stage", None) or []
+        if stage:
+            # the estimator loops stage their batches by hand and the ps workers push per-batch gradients: neither
+            # runs the staging launch that applies the input stage (Model.fit does)
+            names = ", ".join(f"{l.name} ({type(l).__name__})" for l in stage)
+            if isinstance(st, ParameterServerStrategy):
+                raise NotImplementedError(f"ParameterServerStrategy does not support a model with an input stage "
+                                          f"({names}): train it with Model.fit under a synchronous strategy")
+            raise NotImplementedError(f"Estimator training (model_to_estimator) does not support a model with an "
+                                      f"input stage ({names}): train it with Model.fit")
         if isinstance(st, ParameterServerStrategy) and st.is_distributed:
             from ..optimizers import FUSED_KINDS
             opt = self.model.optimizer

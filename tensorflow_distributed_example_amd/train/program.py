@@ -601,7 +601,7 @@ def match_convnet(model, loss):
     MaxPooling2D(2) · Flatten · Dense(bias[,relu]) · Dense(bias[,softmax]) + softmax-CE with a trivial spec
     (the sparse loss, or the categorical one without label smoothing; no class weights)."""
     from .. import losses as LS
-    ls = [l for l in model.layers if not isinstance(l, L.InputLayer)]
+    ls = [l for l in model.body_layers if not isinstance(l, L.InputLayer)]   # (without the input stage)
     if ls and isinstance(ls[0], L.Reshape) and len(ls[0].target_shape) == 3:
         ls = ls[1:]
     if len(ls) != 5 or not LS.is_softmax_ce(loss):

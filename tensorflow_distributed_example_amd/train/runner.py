@@ -133,6 +133,23 @@ class Program:
         self.y_ring = [torch.zeros((self.S, self.B), dtype=torch.int32, device=d) for d in self.devices]
         self.x_stage = [_Stager((self.S, self.B) + xs, torch.float32, d) for d in self.devices]
         self.y_stage = [_Stager((self.S, self.B), torch.int32, d) for d in self.devices]
+        # the model's input stage (RandomFlip / RandomTranslation): a training program applies it in the launch
+        # that fills the x ring (``DeviceFeed.stage``), or -- host-staged groups, partial batches -- stages x into
+        # a scratch buffer of the ring's size and runs the same launch from there into the ring (``_augment``)
+        self.aug = None
+        stage = model.input_stage if training else []
+        if stage:
+            from ..ops import augment as AU
+            if xdt not in (torch.float32, torch.bfloat16):
+                # the staging launch moves float32 or bfloat16 rows: refused here, not at the first step of a fit
+                names = ", ".join(f"{l.name} ({type(l).__name__})" for l in stage)
+                raise NotImplementedError(f"model {model.name!r}: the input stage ({names}) is applied to a float32 or "
+                                          f"bfloat16 input ring; the {self.plans[0].kind} plan takes {xdt}")
+            self.aug = AU.stage_spec(stage)
+            self._aug_src = [torch.zeros_like(t) for t in self.x_ring]
+            self._aug_bad = [torch.zeros(1, dtype=torch.int32, device=d) for d in self.devices]
+            if any(d.type == "cuda" for d in self.devices):
+                AU.check_abi(N.hip())
         self.graph = None          # the last captured graph (diagnostics)
         self.graphs = {}           # start parities -> (hipGraph of one execution, end parities)
         self._graph_key = None
@@ -269,11 +286,30 @@ class Program:
                 p.set_class_weight(table)
 
     # ------------------------------------------------------------------ staging
-    def stage(self, per_replica_steps):
-        """per_replica_steps[r] = (x [S,B,...], y [S,B]) for local replica r."""
+    def _augment(self, r, n, B, step0):
+        """The input stage over the first ``n`` rows of replica r's scratch buffer into its x ring: row i is
+        local row ``i % B`` of global step ``step0 + i // B``.  The HIP launch on a GPU, the numpy twin on a
+        CPU replica (the reference plan)."""
+        from ..ops import augment as AU
+        src, ring = self._aug_src[r], self.x_ring[r]
+        if ring.is_cuda:
+            AU.stage_rows(src, n, None, n, B, self.x_shape, ring, self.aug, step0, self._aug_bad[r])
+            return
+        per = int(np.prod(self.x_shape))
+        x = src.view(-1)[: n * per].float().numpy().reshape((n,) + tuple(self.x_shape))
+        ring.view(-1)[: n * per].copy_(torch.from_numpy(AU.apply(self.aug, x, B, step0)).reshape(-1))
+
+    def stage(self, per_replica_steps, step0=0):
+        """per_replica_steps[r] = (x [S,B,...], y [S,B]) for local replica r; ``step0``: the global step of the
+        group's first batch (the input stage draws by it)."""
         for r, (x, y) in enumerate(per_replica_steps):
             with _ctx(self.devices[r]):
                 xr, yr = self.x_ring[r], self.y_ring[r]
+                if self.aug is not None:
+                    self.x_stage[r].stage(x, self._aug_src[r])
+                    self.y_stage[r].stage(y, yr)
+                    self._augment(r, self.S * self.B, self.B, step0)
+                    continue
                 if _same_device_pair(x, xr) and _same_device_pair(y, yr):
                     # a device-resident batch group: x and y into the ring in ONE copy launch
                     N.check(N.hip().tde_copy_pairs(
@@ -570,13 +606,18 @@ class Program:
                 p.refresh()
             self._steps(self.S)
 
-    def run_single(self, per_replica, global_actual):
-        """One (possibly partial) step executed eagerly. per_replica[r] = (x[B_r,...], y[B_r])."""
+    def run_single(self, per_replica, global_actual, step0=0):
+        """One (possibly partial) step executed eagerly. per_replica[r] = (x[B_r,...], y[B_r]); ``step0``: its
+        global step (the input stage draws by it, with the batch's own row count)."""
         self._warm_comm()
         for r, (x, y) in enumerate(per_replica):
             with _ctx(self.devices[r]):
                 n = len(y)
-                self.x_stage[r].stage(x, self.x_ring[r][0])
+                if self.aug is not None and n > 0:
+                    self.x_stage[r].stage(x, self._aug_src[r][0])
+                    self._augment(r, n, n, step0)
+                else:
+                    self.x_stage[r].stage(x, self.x_ring[r][0])
                 self.y_stage[r].stage(y, self.y_ring[r][0])
         for p in self.plans:
             p.refresh()
