@@ -664,8 +664,10 @@ __global__ __launch_bounds__(NTHH) void head_kernel(HeadArgs a) {
     }
     mu[f] = mean;
     rs[f] = rstd;
+    // y = (h - mean) * sc + beta, the mean subtracted first: a shift beta - mean*sc folded into one constant
+    // rounds at |mean|*sc, which swamps beta when the batch variance is ~0 (rstd = 1/sqrt(eps): a 1-row step)
     sc[f] = f < D ? gm * rstd : 0.f;
-    sh[f] = f < D ? bt - mean * gm * rstd : 0.f;
+    sh[f] = f < D ? bt : 0.f;
   }
   lds_barrier();
   stamp(a.stamps, 1);
@@ -679,8 +681,9 @@ __global__ __launch_bounds__(NTHH) void head_kernel(HeadArgs a) {
       const int r = dq(e, a.dDp), ff = e - r * Dp;
       float act = 0.f, xh = 0.f;
       if (r0 + r < B && ff < D) {
-        xh = (hv[u] - mu[ff]) * rs[ff];
-        act = fmaxf(fmaf(hv[u], sc[ff], sh[ff]), 0.f);
+        const float d = hv[u] - mu[ff];
+        xh = d * rs[ff];
+        act = fmaxf(fmaf(d, sc[ff], sh[ff]), 0.f);
         if (a.drop_on && !quad) act *= keep_scale(a.rate, a.seed, it, a.layer_id, (long long)(r0 + r) * D + ff);
       }
       As[r * kHLD + ff] = act;
@@ -964,7 +967,7 @@ __global__ __launch_bounds__(NTB) void dense_bwd_kernel(DenseBwdArgs a, HeadFold
       mu[f] = mean;
       rsd[f] = rstd;
       scd[f] = coef;
-      shd[f] = f < D ? bt - mean * gm * rstd : 0.f;
+      shd[f] = f < D ? bt : 0.f;   // y = (h - mean) * sc + beta, as the head launch
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -985,8 +988,9 @@ __global__ __launch_bounds__(NTB) void dense_bwd_kernel(DenseBwdArgs a, HeadFold
           const int rl = rt * 16 + fq * 4 + i;
           float act = 0.f, x = 0.f;
           if (rl < B && fe < D) {
-            x = (hv[j][i] - m_) * r_;
-            act = fmaxf(fmaf(hv[j][i], s_, h_), 0.f);
+            const float d = hv[j][i] - m_;
+            x = d * r_;
+            act = fmaxf(fmaf(d, s_, h_), 0.f);
             if (hf.keep) act = ((kw[j] >> (8 * i)) & 1u) ? act * hf.inv_keep : 0.f;
           }
           As[rl * ldA + fe] = act;
@@ -1861,6 +1865,22 @@ TDE_API int tde_bncnn_conv_fwd_cfg(const TdeBnGeo* gg, int* out) {
   return rc;
 }
 
+// Fewest rows of a training forward of this layer that can stage the class-stacked input-gradient weights of
+// its backward (tde_bncnn_conv_fwd wstack: one element per thread of the (B, msplit) grid); 0 when the layer has
+// no staged stack (it does not plan, or the stack does not fit the backward's registers).  A step with fewer
+// rows passes no wstack to the forward and the backward, which then gathers the weights itself.
+static int conv_stack_rows(const ConvFwdP& P, const ConvBwdP& S) {
+  if (!S.wgather) return 0;
+  const int per_row = P.msplit * NTB;
+  return std::max(1, (S.Kdp * S.NP + per_row - 1) / per_row);
+}
+TDE_API int tde_bncnn_conv_stack_rows(const TdeBnGeo* gg) {
+  ConvFwdP P;
+  ConvBwdP S;
+  if (conv_fwd_plan(geo_of(gg), P) != 0 || conv_bwd_plan(P.g, 1, S) != 0) return 0;
+  return conv_stack_rows(P, S);
+}
+
 // z = conv(relu(BN_in(in))); this layer's BN partial sums into acc [B][2][Co] (nullable).
 // inc_iter (nullable): the step counter a training step's first launch advances.
 TDE_API int tde_bncnn_conv_fwd(const TdeBnGeo* gg, int B, const float* in, const TdeBn* bn_in, const float* w, float* z,
@@ -1871,7 +1891,7 @@ TDE_API int tde_bncnn_conv_fwd(const TdeBnGeo* gg, int B, const float* in, const
   ConvFwdArgs a{P, B, in, bn_of(bn_in), w, z, acc, next_stamps(), inc_iter, wstack, ConvBwdP{}};
   if (wstack) {
     // the whole stack must be covered by the grid's threads, and fit the backward's registers
-    if (conv_bwd_plan(P.g, 1, a.sp) != 0 || !a.sp.wgather || a.sp.Kdp * a.sp.NP > B * P.msplit * NTB) return -3;
+    if (conv_bwd_plan(P.g, 1, a.sp) != 0 || !a.sp.wgather || B < conv_stack_rows(P, a.sp)) return -3;
   }
   set_lds(conv_fwd_kernel, P.lds);
   conv_fwd_kernel<<<dim3(B, P.msplit), NTB, P.lds, stream>>>(a);

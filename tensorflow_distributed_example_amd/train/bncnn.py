@@ -32,6 +32,7 @@ from ..ops.kernels import BnOpt, opt_hyper, opt_slots
 from .program import OptimizerKernel, ReplicaPlan
 
 BN_NONE, BN_TRAIN, BN_MOVING, BN_BATCH, BN_SAVED = 0, 1, 2, 3, 4
+MAX_FLAT = 1536   # dense_fwd_kernel: 16 waves x 4 x kDS K steps (csrc/kernels/bncnn.hip)
 
 _vp, _i = C.c_void_p, C.c_int
 N.register_hip({
@@ -52,6 +53,7 @@ N.register_hip({
     "tde_bncnn_dense_bwd_head": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp,
                                       C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tde_bncnn_conv_bwd_plan": (_i, [_vp, _i, _vp]),
+    "tde_bncnn_conv_stack_rows": (_i, [_vp]),
     # geo, B, z, bn, bb, gout, w, in, bn_in, gin, acc_in, dwpart, dgrad, wstack, stream
     "tde_bncnn_conv_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     # n, cnt, part, out, len, opt, push_seg, push, stream
@@ -132,6 +134,9 @@ def match_bncnn(model, loss):
         return None
     if d.units > 256:
         too_wide.append(f"{d.name}: {d.units} units (<= 256)")
+    flat = int(np.prod(convs[-1][0].output_shape))
+    if flat > MAX_FLAT:
+        too_wide.append(f"{d.name}: {flat} flattened inputs (<= {MAX_FLAT})")
     bn_d = ls[i + 1]
     i += 3
     drop = None
@@ -211,9 +216,13 @@ class BnCnnPlan(ReplicaPlan):
             blk["bwd"] = list(out)
             # the input-gradient role's class-stacked weights, staged by the training forward of the layer
             blk["wstack"] = torch.zeros(out[5], **f32) if li > 0 and out[5] > 0 else None
+            # ... when the step has the rows: one forward thread per stack element
+            blk["stack_rows"] = self.lib.tde_bncnn_conv_stack_rows(C.byref(blk["geo"])) if li > 0 else 0
         dense, bn_d, drop = spec["dense"]
         last = self.blocks[-1]
         self.K = last["geo"].Ho * last["geo"].Wo * last["geo"].Co
+        if self.K > MAX_FLAT:
+            raise ValueError(f"{dense.name}: {self.K} flattened inputs (<= {MAX_FLAT})")
         self.D = dense.units
         self.Dp = -(-self.D // 16) * 16
         self.dense = dense
@@ -282,6 +291,11 @@ class BnCnnPlan(ReplicaPlan):
                   float(blk["eps"]), float(blk["momentum"]), float(R / max(R - 1, 1)), _P(blk["mmean"]),
                   _P(blk["mvar"]), _P(blk["saved"]))
 
+    def _wstack(self, blk, B):
+        """The staged class-stacked weights of a B-row training step, or None: below ``stack_rows`` rows the
+        forward's grid has fewer threads than the stack has elements, and the backward gathers the weights."""
+        return blk["wstack"] if blk["wstack"] is not None and B >= blk["stack_rows"] > 0 else None
+
     def _fwd_mode(self, training):
         if training == "train":
             return BN_TRAIN
@@ -298,7 +312,7 @@ class BnCnnPlan(ReplicaPlan):
         for li, blk in enumerate(self.blocks):
             # a training step's first launch advances the step counter (dropout seed, Adam's t)
             inc = _P(self.iterations) if (phase == "train" and li == 0) else None
-            ws = _P(blk["wstack"]) if phase == "train" else None
+            ws = _P(self._wstack(blk, B)) if phase == "train" else None
             rc = lib.tde_bncnn_conv_fwd(C.byref(blk["geo"]), B, _P(inp), C.byref(bn_in), _P(blk["w"]), _P(blk["z"]),
                                         _P(blk["acc"]) if batch_stats else None, inc, ws, s)
             if rc != 0:
@@ -394,7 +408,7 @@ class BnCnnPlan(ReplicaPlan):
             rc = lib.tde_bncnn_conv_bwd(C.byref(blk["geo"]), B, _P(blk["z"]), C.byref(self._bn(blk, BN_SAVED, B)),
                                         C.byref(bb), _P(blk["g"]), _P(blk["w"]), _P(inp), C.byref(bn_in), _P(gin),
                                         _P(acc_in), _P(blk["dwpart"]), int(li > 0),
-                                        _P(blk["wstack"]) if li > 0 else None, s)
+                                        _P(self._wstack(blk, B)) if li > 0 else None, s)
             if rc != 0:
                 raise RuntimeError(f"tde_bncnn_conv_bwd({blk['conv'].name}) failed with {rc}")
         # weight-gradient partials -> the bucket: per image for the convs, per 64-row block for the dense
@@ -485,5 +499,7 @@ def try_make(model, store, device, batch, global_batch, optimizer, loss):
         return None
     try:
         return BnCnnPlan(model, store, device, batch, global_batch, optimizer, loss, spec)
-    except ValueError:
+    except ValueError as e:   # a geometry the kernels' planners refuse: said, not silent
+        import warnings
+        warnings.warn(f"model {model.name!r}: no fused BN-CNN step ({e}); running the per-layer kernel plan")
         return None

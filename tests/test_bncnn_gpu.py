@@ -2,104 +2,25 @@
 vs float64 autograd oracles: every gradient <= 1e-5 relative (norm-wise), BN moving statistics, the
 loss / accuracy metrics, evaluation with moving statistics and prediction.
 
-The oracle takes each ReLU decision from the plan's own f32 pre-activations (its stored raw conv /
-dense outputs and saved batch statistics): a pre-activation within one f32 ulp of zero may be decided
-differently in f64, and a flipped ReLU moves a whole gradient element; everything else is f64."""
+The oracle (tests/bncnn_oracle.py, shared with the family suite tests/test_bncnn_family_gpu.py) takes each ReLU
+decision from the plan's own f32 pre-activations (its stored raw conv / dense outputs and saved batch
+statistics): a pre-activation within one f32 ulp of zero may be decided differently in f64, and a flipped ReLU
+moves a whole gradient element; everything else is f64."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from bncnn_cases import model_b as _model_b, model_b_data
+from bncnn_oracle import plan_oracle as _oracle, rel as _rel
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("fp32_policy")]
 
 DEV = "cuda"
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _model_b(tde, rate=0.0, opt=None):
-    L = tde.layers if hasattr(tde, "layers") else tde.keras.layers
-    m = tde.Sequential([
-        L.Reshape(input_shape=(28 * 28,), target_shape=(28, 28, 1)),
-        L.Conv2D(filters=6, kernel_size=3, padding="same", use_bias=False),
-        L.BatchNormalization(scale=False, center=True),
-        L.Activation("relu"),
-        L.Conv2D(filters=12, kernel_size=6, padding="same", use_bias=False, strides=2),
-        L.BatchNormalization(scale=False, center=True),
-        L.Activation("relu"),
-        L.Conv2D(filters=24, kernel_size=6, padding="same", use_bias=False, strides=2),
-        L.BatchNormalization(scale=False, center=True),
-        L.Activation("relu"),
-        L.Flatten(),
-        L.Dense(200, use_bias=False),
-        L.BatchNormalization(scale=False, center=True),
-        L.Activation("relu"),
-        L.Dropout(rate),
-        L.Dense(10, activation="softmax"),
-    ])
-    m.compile(loss="sparse_categorical_crossentropy", optimizer=opt or tde.optimizers.SGD(0.01), metrics=["accuracy"])
-    m.build()
-    # non-trivial BN betas / moving statistics
-    g = torch.Generator(device="cpu").manual_seed(3)
-    for n in m._store.names():
-        if n.endswith("/beta"):
-            v = m._store.view(n)
-            v.copy_((torch.rand(v.shape, generator=g) - 0.5).to(v.device) * 0.2)
-    return m
-
-
 def _data(B, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    x = torch.rand(B, 784, generator=g).to(DEV)
-    y = torch.randint(0, 10, (B,), generator=g).int().to(DEV)
-    return x, y
-
-
-def _oracle(plan, x, y, B, drop_mask=None):
-    """float64 autograd of the plan's model at the store's weights; ReLU decisions from the plan's f32
-    pre-activations (after plan.train_step); ``drop_mask`` [B, D] (keep scales) applied after the dense
-    BN's ReLU when given.  Returns ({var: grad}, {moving var: new value}, loss)."""
-    st = plan.store
-    dd = torch.float64
-    W = {n: st.view(n).detach().to(dd).clone().requires_grad_(st.segments[n].trainable) for n in st.order}
-    a = x[:B].to(dd).view(B, 28, 28, 1)
-    moving = {}
-    for blk in plan.blocks:
-        conv, bn = blk["conv"], blk["bn"]
-        (pt, pb), (pl, pr) = conv.pads(conv.input_shape)
-        z = F.conv2d(F.pad(a.permute(0, 3, 1, 2), (pl, pr, pt, pb)), W[f"{conv.name}/kernel"].permute(3, 2, 0, 1),
-                     stride=conv.strides).permute(0, 2, 3, 1)
-        mean, var = z.mean((0, 1, 2)), z.var((0, 1, 2), unbiased=False)
-        pre = (z - mean) / torch.sqrt(var + bn.epsilon) + W[f"{bn.name}/beta"]
-        g = blk["geo"]
-        z32 = blk["z"][: B * g.Ho * g.Wo * g.Co].view(B, g.Ho, g.Wo, g.Co)
-        s = blk["saved"]
-        mask = ((z32 - s[: g.Co]) * s[g.Co:] + st.view(f"{bn.name}/beta")) > 0
-        a = pre * mask
-        R = B * g.Ho * g.Wo
-        moving[f"{bn.name}/moving_mean"] = W[f"{bn.name}/moving_mean"] * bn.momentum + mean.detach() * (1 - bn.momentum)
-        moving[f"{bn.name}/moving_variance"] = (W[f"{bn.name}/moving_variance"] * bn.momentum
-                                                + var.detach() * R / (R - 1) * (1 - bn.momentum))
-    h = a.reshape(B, -1) @ W[f"{plan.dense.name}/kernel"]
-    bnl = plan.bnd["layer"]
-    mean, var = h.mean(0), h.var(0, unbiased=False)
-    pre = (h - mean) / torch.sqrt(var + bnl.epsilon) + W[f"{bnl.name}/beta"]
-    h32 = plan.h[: B * plan.Dp].view(B, plan.Dp)[:, : plan.D]
-    sv = plan.bnd["saved"]
-    mask = ((h32 - sv[: plan.D]) * sv[plan.D:] + st.view(f"{bnl.name}/beta")) > 0
-    a = pre * mask
-    if drop_mask is not None:
-        a = a * drop_mask[:B].to(dd)
-    moving[f"{bnl.name}/moving_mean"] = W[f"{bnl.name}/moving_mean"] * bnl.momentum + mean.detach() * (1 - bnl.momentum)
-    moving[f"{bnl.name}/moving_variance"] = W[f"{bnl.name}/moving_variance"] * bnl.momentum + var.detach() * (
-        1 - bnl.momentum)
-    logits = a @ W[f"{plan.head.name}/kernel"] + W[f"{plan.head.name}/bias"]
-    loss = F.cross_entropy(logits, y[:B].long(), reduction="sum") * plan.scale
-    loss.backward()
-    return {n: W[n].grad for n in st.names(trainable=True)}, moving, loss.item() / plan.scale / B, logits.detach()
+    return model_b_data(B, seed, DEV)
 
 
 @pytest.mark.parametrize("B", [128, 50])

@@ -69,6 +69,34 @@ def test_bncnn_family_near_miss_warns():
             assert spec is None and len(msgs) == 1 and "48 channels" in msgs[0] and "400 units" in msgs[0], msgs
 
 
+def test_bncnn_family_flattened_width_past_the_dense_kernel_warns():
+    """28x28x1 · Conv2D(6, 3, same) · BN · ReLU · Flatten has K = 4704 flattened inputs, past the fused dense
+    forward's 1536: a near miss that warns and runs per layer, like the channel / unit / class limits; the same
+    block at stride 2 on a 14x14 image (K = 294) matches silently."""
+    import tensorflow_distributed_example_amd as tde
+    from tensorflow_distributed_example_amd.models import layers as L
+    from tensorflow_distributed_example_amd.train import bncnn
+    tde.backend.set_global_policy("float32")
+    try:
+        for shape, strides, fused in (((28, 28, 1), 1, False), ((14, 14, 1), 2, True)):
+            m = tde.models.Sequential([
+                L.Conv2D(6, 3, strides=strides, padding="same", use_bias=False, input_shape=shape),
+                L.BatchNormalization(), L.Activation("relu"), L.Flatten(), L.Dense(32, use_bias=False),
+                L.BatchNormalization(), L.Activation("relu"), L.Dense(10, activation="softmax")])
+            loss = tde.losses.SparseCategoricalCrossentropy()
+            with warnings.catch_warnings(record=True) as rec:
+                warnings.simplefilter("always")
+                spec = bncnn.match_bncnn(m, loss)
+            msgs = [str(w.message) for w in rec]
+            if fused:
+                assert spec is not None and not msgs, msgs
+            else:
+                assert spec is None and len(msgs) == 1 and "4704 flattened inputs (<= 1536)" in msgs[0] \
+                    and "per-layer kernel plan" in msgs[0], msgs
+    finally:
+        tde.backend.set_global_policy(None)
+
+
 def test_python_fit_rule_matches_the_kernel_family():
     """train/program.gen_fits mirrors the kernels' instantiation rule (csrc/kernels/convnet_gen.hip): 27 of
     the 32 (filters, units) pairs."""
