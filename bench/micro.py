@@ -4,7 +4,9 @@
 * launch floor: empty-kernel cost, eager and inside a hipGraph;
 * per-kernel standalone time: each kernel of the step replayed 200x in a graph;
 * phase stamps: s_memrealtime stamps at phase boundaries of each workgroup
-  (diagnostic only) -> where inside each kernel the time goes.
+  (diagnostic only) -> where inside each kernel the time goes.  The float32 kernels given a stamp buffer
+  are the general forms (csrc/kernels/convnet_f32.hip): the stamps locate the phases, the graph times above
+  them (no stamp buffer) are the production forms'.
 Prints one JSON object; used to build profiles/*.md.
 """
 from __future__ import annotations

@@ -287,6 +287,20 @@ struct BwdArgs {
   XgPush push;                       // MODE 0, nranks > 0: dW1 goes to the xGMI owners (fused DP exchange)
 };
 
+// What a form of the float32 backward knows at compile time, next to its image geometry (convnet_f32.hip: Geo).
+//   DIAG   the phase stamps exist (off: stamp / stamp_fine / stamp_landed are not called at all: a template
+//          flag, not dead-code elimination; the form then ignores BwdArgs::stamps)
+//   WHOLE  B is a multiple of 64: every chunk holds 64 images, no index is clamped and no row is masked
+//   NREP   the hpre replica count (0: BwdArgs::hrep, by a uniform switch)
+// The default (and the bf16 kernels') form knows nothing: it serves every call.
+template <bool DIAG, bool WHOLE, int NREP>
+struct BwdForm {
+  static constexpr bool kDiag = DIAG, kWhole = WHOLE;
+  static constexpr int kRep = NREP;
+  __device__ __forceinline__ static int nb(const BwdArgs& a, int b0) { return WHOLE ? 64 : min(64, a.B - b0); }
+};
+using BwdFormAny = BwdForm<true, false, 0>;
+
 // Up to NPER elements per thread of a FlatApply's ranges, loaded early into registers and
 // updated later (the loads' latency hides behind the caller's work).
 template <int NPER>
@@ -396,20 +410,22 @@ __device__ __forceinline__ int opaque_tid() {
 // HpreRep<N> holds hrep <= N replicas in N float4 (N a compile-time count: 4 replicas cost 16 registers,
 // not the 32 of the largest count): issue() is straight-line, a replica past hrep reads replica hrep-1
 // and counts as 0 in sum() (replica order).  load_hpre_sw() picks the count by a uniform switch on hrep.
+// EXACT: hrep == N (a host check): no clamp and no select.
 constexpr int kMaxRep = 8;
-template <int N>
+template <int N, bool EXACT = false>
 struct HpreRep {
   float4 v[N];
   __device__ __forceinline__ void issue(const BwdArgs& a, int row, int c4) {
 #pragma unroll
     for (int r = 0; r < N; ++r)
-      v[r] = *reinterpret_cast<const float4*>(a.hpre + (size_t)min(r, a.hrep - 1) * a.hrep_stride + (size_t)row * HD + c4);
+      v[r] = *reinterpret_cast<const float4*>(a.hpre + (size_t)(EXACT ? r : min(r, a.hrep - 1)) * a.hrep_stride +
+                                              (size_t)row * HD + c4);
   }
   __device__ __forceinline__ float4 sum(const BwdArgs& a) const {
     float4 s = v[0];
 #pragma unroll
     for (int r = 1; r < N; ++r) {
-      const bool on = r < a.hrep;
+      const bool on = EXACT || r < a.hrep;
       s.x += on ? v[r].x : 0.f; s.y += on ? v[r].y : 0.f; s.z += on ? v[r].z : 0.f; s.w += on ? v[r].w : 0.f;
     }
     return s;
@@ -439,6 +455,17 @@ __device__ __forceinline__ float4 load_hpre_sw(const BwdArgs& a, int row, int c4
     default: return load_hpre_n<8>(a, row, c4);
   }
 }
+// The replica count of the form F (BwdForm::kRep), or the switch
+template <class F>
+__device__ __forceinline__ float4 load_hpre_form(const BwdArgs& a, int row, int c4) {
+  if constexpr (F::kRep > 0) {
+    HpreRep<(F::kRep > 0 ? F::kRep : 1), true> h;
+    h.issue(a, row, c4);
+    return h.sum(a);
+  } else {
+    return load_hpre_sw(a, row, c4);
+  }
+}
 // kMaxRep slots whatever hrep is (the bf16 kernels)
 __device__ __forceinline__ float4 load_hpre(const BwdArgs& a, int row, int c4) {
   if (a.hrep > kMaxRep) return load_hpre_loop(a, row, c4);
@@ -455,12 +482,13 @@ __device__ __forceinline__ float4 load_hpre(const BwdArgs& a, int row, int c4) {
   return s;
 }
 
-// h = act(hpre + b1) of this thread's row / 4 units into LDS (rows past nb zeroed)
+// h = act(hpre + b1) of this thread's row / 4 units into LDS (rows past nb zeroed; whole chunks have none)
+template <class F = BwdFormAny>
 __device__ __forceinline__ void head_stage(const BwdArgs& a, float4 hv, float4 b1v, int hr, int hc4, int nb,
                                            float* hs) {
   float4 h = float4{hv.x + b1v.x, hv.y + b1v.y, hv.z + b1v.z, hv.w + b1v.w};
   if (a.pre_relu) h = float4{fmaxf(h.x, 0.f), fmaxf(h.y, 0.f), fmaxf(h.z, 0.f), fmaxf(h.w, 0.f)};
-  if (hr >= nb) h = float4{0.f, 0.f, 0.f, 0.f};
+  if (!F::kWhole && hr >= nb) h = float4{0.f, 0.f, 0.f, 0.f};
   *reinterpret_cast<float4*>(hs + hr * HS + hc4) = h;
 }
 
@@ -527,7 +555,8 @@ __device__ __forceinline__ void stamp_fine(long long* st, int slot) {
 // the four partials in the order ((kq0 + kq1) + kq2) + kq3 and does the one softmax row set
 // rt*16 + 4*fq + i: one iteration per wave, not four on four waves while twelve wait.
 // METRICS = false (the trunk workgroups): loss / arg-max / count are not computed at all.
-template <bool METRICS>
+// F: the form's row masks (none with whole chunks) and fine stamp.
+template <bool METRICS, class F = BwdFormAny>
 __device__ __forceinline__ void head_logits_ce16(const BwdArgs& a, int nb, const HeadLds& l, float* part0, int lane,
                                                  int wave, float& la, float& ca, float& na) {
   const int fr = lane & 15, fq = lane >> 4, C = a.C;
@@ -542,14 +571,14 @@ __device__ __forceinline__ void head_logits_ce16(const BwdArgs& a, int nb, const
     for (int i = 0; i < 4; ++i) dst[i * 64] = lg[i];
   }
   lds_barrier();
-  stamp_fine(a.stamps, 10);
+  if constexpr (F::kDiag) stamp_fine(a.stamps, 10);
   {
     const int rt = wave & 3, i = wave >> 2;
     const int o = rt * 256 + i * 64 + lane;
     const float p0 = part0[o], p1 = l.part[o], p2 = l.part[1024 + o], p3 = l.part[2048 + o];
     const float lgi = ((p0 + p1) + p2) + p3;
     const int r = rt * 16 + fq * 4 + i;
-    const bool valid = r < nb;
+    const bool valid = F::kWhole || r < nb;
     const bool cv = fr < C;
     const float z = cv ? lgi + l.b2s[fr] : -3.0e38f;
     const float m = row16_max(z);
@@ -573,6 +602,7 @@ __device__ __forceinline__ void head_logits_ce16(const BwdArgs& a, int nb, const
 
 // dH tile of this wave (rows rt*16.., units ut*16.., rt = wave>>2, ut = wave&3) = dl . W2^T, masked
 // by h > 0 and rows < nb.  Lane holds dH[rt*16 + 4fq + i][ut*16 + fr].
+template <class F = BwdFormAny>
 __device__ __forceinline__ f32x4 head_dh(const BwdArgs& a, int nb, const HeadLds& l, int lane, int wave) {
   const int fr = lane & 15, fq = lane >> 4, rt = wave >> 2, ut = wave & 3;
   f32x4 gh = {0.f, 0.f, 0.f, 0.f};
@@ -583,7 +613,7 @@ __device__ __forceinline__ f32x4 head_dh(const BwdArgs& a, int nb, const HeadLds
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = rt * 16 + fq * 4 + i;
-    if ((a.pre_relu && !(l.hs[r * HS + j] > 0.f)) || r >= nb) gh[i] = 0.f;
+    if ((a.pre_relu && !(l.hs[r * HS + j] > 0.f)) || (!F::kWhole && r >= nb)) gh[i] = 0.f;
   }
   return gh;
 }
@@ -604,8 +634,9 @@ __device__ __forceinline__ long long head_var(const BwdArgs& a, int tid, int i) 
 // db1p: 256 floats of LDS scratch outside the head areas (LEAN: 1024, which also hold the logits' first
 // K-quarter partial inside the chunk loop and the 16 waves' metrics after it).
 // LEAN (the float32 kernels, which must stay out of scratch): thread indices from opaque_tid() inside the
-// chunk loop and at the update, replica slots by switch.
-template <int MODE, bool LEAN = false>
+// chunk loop and at the update, replica slots by switch or, like the row masks and stamp 7, as the form F has
+// them.
+template <int MODE, bool LEAN = false, class F = BwdFormAny>
 __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& l, float* db1p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
   const int fr = lane & 15, fq = lane >> 4, C = a.C;
@@ -636,21 +667,21 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
   f32x4 gw = {0.f, 0.f, 0.f, 0.f};
   float db1acc = 0.f, db2acc = 0.f, la = 0.f, ca = 0.f, na = 0.f;
   for (int b0 = 0; b0 < a.B; b0 += 64) {
-    const int nb = min(64, a.B - b0);
+    const int nb = F::nb(a, b0);
     // this iteration's own copies of the thread indices (opaque_tid())
     const int tid = LEAN ? opaque_tid() : (int)threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int hr = tid >> 4, hc4 = (tid & 15) * 4;
     float4 hv = {0.f, 0.f, 0.f, 0.f};
-    if (hr < nb) hv = LEAN ? load_hpre_sw(a, b0 + hr, hc4) : load_hpre(a, b0 + hr, hc4);
+    if (hr < nb) hv = LEAN ? load_hpre_form<F>(a, b0 + hr, hc4) : load_hpre(a, b0 + hr, hc4);
     const int lab = (tid < nb) ? a.labels[b0 + tid] : 0;
-    head_stage(a, hv, b1v, hr, hc4, nb, l.hs);
+    head_stage<F>(a, hv, b1v, hr, hc4, nb, l.hs);
     if (tid < 64) l.labs[tid] = lab;
     lds_barrier();
     // LEAN: softmax-CE on all 16 waves (partial 0 in the otherwise unused db1p area until the loop ends)
-    if (LEAN) head_logits_ce16<true>(a, nb, l, db1p, lane, wave, la, ca, na);
+    if (LEAN) head_logits_ce16<true, F>(a, nb, l, db1p, lane, wave, la, ca, na);
     else head_logits_ce(a, nb, l, lane, wave, la, ca, na);
-    const f32x4 gh = head_dh(a, nb, l, lane, wave);
+    const f32x4 gh = head_dh<F>(a, nb, l, lane, wave);
     db1acc += (gh[0] + gh[1]) + (gh[2] + gh[3]);
     if (wave < 4) {
 #pragma unroll
@@ -722,7 +753,7 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (gdst[i]) *gdst[i] += gv[i];
-    stamp(a.stamps, 7);
+    if constexpr (F::kDiag) stamp(a.stamps, 7);
     return;
   }
   const float lr_t = opt_lr_t(a.h, t_it);
@@ -745,7 +776,7 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
     if (a.pend_set) *a.pend_set = 1;
     if (a.iter_prev) *a.iter_prev = t_it;
   }
-  stamp(a.stamps, 7);   // diagnostics: the head workgroup's end (micro.py)
+  if constexpr (F::kDiag) stamp(a.stamps, 7);   // diagnostics: the head workgroup's end (micro.py)
 }
 
 // Reduces the routing accumulators (conv weight / bias gradients: [tap 0..8 | bias 9][CC]) of the

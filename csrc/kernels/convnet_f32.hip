@@ -26,6 +26,19 @@
 // (168 = 40 mod 64 for the forward's 128-wide tile, 8-k groups per position: a position's column
 // offset shifts every lane's bank alike), the ds_read_b128 lane groups hit disjoint banks (searched
 // exhaustively over strides and per-group rotations).
+//
+// Each launch has a production form and a general one, picked by the entry points:
+//   forward   convnet32_fwd_plain_kernel: no stamp buffer given (every training and inference step);
+//             convnet32_fwd_kernel: the same body with its five phase stamps, for calls with a stamp buffer.
+//   backward  convnet32g_bwd_kernel<MODE>: 28 x 28 images, B a positive multiple of 64 (whole chunks: no index
+//             clamped, no row masked), 4 hpre replicas, no stamp buffer -- all compile-time constants
+//             (Geo<28, 28>, ProdForm), and no diagnostics in the kernel text.  This is the step of the
+//             reference model at its batch of 64 per worker;
+//             convnet32_bwd_kernel<MODE>: every other call (other shapes, ragged batches, other replica counts,
+//             the deterministic layout, a stamp buffer): everything read from the arguments, stamps included.
+//             tde_convnet_f32_runtime_geom(1) forces it.
+// A diagnostic run (bench/micro.py with a stamp buffer) therefore times the general forms: its stamps locate
+// the phases, the production forms' times come from runs without a stamp buffer.
 #include "tde_convnet.h"
 
 namespace tde {
@@ -51,8 +64,10 @@ __device__ __forceinline__ int k16_col(int fq, int i) { return fq * 16 + 4 * ((i
 
 // Image geometry of a backward form: GH x GW known at compile time (the 28 x 28 of MNIST, which is all the
 // benchmark and the reference model run: the division by Wp, the workgroup count and every image stride are
-// then constants), or <0, 0>: read from the arguments (every other shape).  The forward keeps the runtime form
-// alone: specialised, it was not faster (profiles/bwd_head/NOTES.md).
+// then constants), or <0, 0>: read from the arguments.  Geo<28, 28> is used by the production form alone
+// (with ProdForm: whole chunks, 4 replicas, no diagnostics); a 28 x 28 call that misses one of
+// its conditions takes Geo<0, 0> like every other shape.  The forward keeps the runtime geometry in both of
+// its forms: specialised, it was not faster (profiles/bwd_head/NOTES.md).
 template <int GH, int GW>
 struct Geo {
   static constexpr bool kFixed = GH > 0;
@@ -91,9 +106,11 @@ struct Fwd32X {
   }
 };
 
-__global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
+// The forward's body.  DIAG: the five phase stamps exist (off: stamp() is not called at all and
+// FwdArgs::stamps is ignored).
+template <bool DIAG>
+__device__ __forceinline__ void convnet32_fwd_body(const FwdArgs& a, unsigned char* fsm) {
   constexpr int NT = 256;
-  extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
   float* As = reinterpret_cast<float*>(fsm);                                  // [FB][AS32] pooled tile
   float* xr = reinterpret_cast<float*>(fsm + FB * AS32 * 4);                  // [FB][XR][W]
   float* wcs = reinterpret_cast<float*>(fsm + FB * AS32 * 4 + kXr32Bytes);    // [10][CC]
@@ -102,7 +119,7 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   int pendv;
   long long iterv;
   conv_flags_issue(a, pendv, iterv);
-  stamp(a.stamps, 0);
+  if constexpr (DIAG) stamp(a.stamps, 0);
   if (a.inc_iter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.inc_iter, 1ull);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
@@ -144,7 +161,7 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
   if (wave == 0 && threadIdx.x < kConvW - NT) wcs[NT + threadIdx.x] = cv1.finish(a, pendv, iterv);
   if (snap_wg) snap.store(a);
   if (a.fly_count && pendv && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.fly_count, 1ull);
-  stamp(a.stamps, 1);
+  if constexpr (DIAG) stamp(a.stamps, 1);
   lds_barrier();
 
   // ---- phase 1: conv + bias + ReLU + 2x2 max-pool; lane = (image fr, position slot fq), wave = 8 channels
@@ -172,9 +189,9 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
     *reinterpret_cast<float4*>(dst) = float4{out[0], out[1], out[2], out[3]};
     *reinterpret_cast<float4*>(dst + 4) = float4{out[4], out[5], out[6], out[7]};
   }
-  stamp(a.stamps, 2);
+  if constexpr (DIAG) stamp(a.stamps, 2);
   lds_barrier();
-  stamp(a.stamps, 3);
+  if constexpr (DIAG) stamp(a.stamps, 3);
 
   // the fragments of positions past P were loaded from the last position: they count as 0
 #pragma unroll
@@ -207,7 +224,17 @@ __global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
     const float s = ((acc[0][r] + acc[1][r]) + acc[2][r]) + acc[3][r];
     if (row < a.B) atomicAdd(hrow + (size_t)row * HD + nt * 16 + fr, s);
   }
-  stamp(a.stamps, 4);
+  if constexpr (DIAG) stamp(a.stamps, 4);
+}
+
+// The forward with its stamps (diagnostic runs: a stamp buffer is given) and the production form without them
+__global__ __launch_bounds__(256) void convnet32_fwd_kernel(FwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
+  convnet32_fwd_body<true>(a, fsm);
+}
+__global__ __launch_bounds__(256) void convnet32_fwd_plain_kernel(FwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
+  convnet32_fwd_body<false>(a, fsm);
 }
 
 // LDS carve of the backward (bytes)
@@ -258,38 +285,44 @@ __device__ __forceinline__ void stamp_landed(long long* st, const Bwd32Chunk& c)
   }
 }
 
-template <int NREP, class G>
+// Whole chunks (F::kWhole, nb == 64): every index lies in the chunk as it is (the label of thread tid is that of
+// image tid & 63; threads < 64 store theirs), so there is no clamp and no select.  F::kRep > 0: exactly NREP replicas.
+template <int NREP, class G, class F>
 __device__ __forceinline__ void bwd32_chunk_issue(const BwdArgs& a, int tid, int p, int py, int px, int b0, int nb,
                                                   Bwd32Chunk& c) {
+  constexpr bool kWhole = F::kWhole;
   const int last = nb - 1;
-  const int hrow = b0 + min(tid >> 4, last), hc4 = (tid & 15) * 4;
-  HpreRep<(NREP > 0 ? NREP : 1)> h;
+  const int hrow = b0 + (kWhole ? tid >> 4 : min(tid >> 4, last)), hc4 = (tid & 15) * 4;
+  HpreRep<(NREP > 0 ? NREP : 1), (F::kRep > 0)> h;
   if (NREP > 0) h.issue(a, hrow, hc4);
-  c.lab = a.labels[b0 + min(tid, last)];
+  c.lab = a.labels[b0 + (kWhole ? tid & 63 : min(tid, last))];
   // the pair starts at an even column <= nb-1; ldPt is even and >= B, so its second float is in the row
   const int pc = (tid & 31) * 2;
   c.ptv = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(a.Pt) + (size_t)(p * CC + (tid >> 5)) * a.ldPt +
-                                           b0 + min(pc, last & ~1));
+                                           b0 + (kWhole ? pc : min(pc, last & ~1)));
   c.xv = float4{0.f, 0.f, 0.f, 0.f};
   c.amv = ~0ull;
   if (tid < 256) {
     const int bl = tid >> 2, r = tid & 3;
-    const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + min(bl, last)) * G::H(a) * G::W(a) +
+    const float2* row = reinterpret_cast<const float2*>(a.x + (size_t)(b0 + (kWhole ? bl : min(bl, last))) * G::H(a) * G::W(a) +
                                                         (2 * py + r) * G::W(a) + 2 * px);
     const float2 u = row[0], t = row[1];
     c.xv = float4{u.x, u.y, t.x, t.y};
     const int cg = tid >> 6, bb = tid & 63;
-    c.amv = a.amax[((size_t)p * (CC / 8) + cg) * a.lda + b0 + min(bb, last)];
+    c.amv = a.amax[((size_t)p * (CC / 8) + cg) * a.lda + b0 + (kWhole ? bb : min(bb, last))];
   }
   c.hv = NREP > 0 ? h.sum(a) : load_hpre_loop(a, hrow, hc4);   // rows past nb: zeroed by head_stage
-  if ((tid >> 2) >= nb) c.xv = float4{0.f, 0.f, 0.f, 0.f};
-  if ((tid & 63) >= nb) c.amv = ~0ull;
-  if (tid >= nb) c.lab = 0;
-  if (pc >= nb) c.ptv.x = 0.f;
-  if (pc + 1 >= nb) c.ptv.y = 0.f;
+  if constexpr (!kWhole) {
+    if ((tid >> 2) >= nb) c.xv = float4{0.f, 0.f, 0.f, 0.f};
+    if ((tid & 63) >= nb) c.amv = ~0ull;
+    if (tid >= nb) c.lab = 0;
+    if (pc >= nb) c.ptv.x = 0.f;
+    if (pc + 1 >= nb) c.ptv.y = 0.f;
+  }
 }
 
-template <int MODE, class G>
+// G: the image geometry; F: what else the form knows (tde_convnet.h: BwdForm)
+template <int MODE, class G, class F>
 __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned char* smem) {
   float* Gs = reinterpret_cast<float*>(smem + kG32);
   float* Gts = reinterpret_cast<float*>(smem + kGt32);
@@ -305,7 +338,7 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
   if (MODE == 2) t_it = *a.iterations;
   // workgroups of the launch: read once, ahead of the first branch (a scalar load); a constant in the fixed form
   const unsigned nwg = G::kFixed ? ((kGH - 2) / 2) * ((kGW - 2) / 2) + 1 : gridDim.x;
-  stamp(a.stamps, 0);
+  if constexpr (F::kDiag) stamp(a.stamps, 0);
   const int W = G::W(a);
   int tid, lane, wave, fr, fq;
   bwd32_ids(tid, lane, wave, fr, fq);
@@ -324,7 +357,7 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
   if (blockIdx.x == nwg - 1) {
     hl.w2s[(tid >> 4) * W2S + (tid & 15)] = (tid & 15) < a.C ? w2v : 0.f;
     if (tid < 16) hl.b2s[tid] = tid < a.C ? b2v : 0.f;
-    head_workgroup<MODE, true>(a, hl, Gs);   // the G area is unused there
+    head_workgroup<MODE, true, F>(a, hl, Gs);   // the G area is unused there
     return;
   }
 
@@ -355,32 +388,37 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
   const float2 w1v = *reinterpret_cast<const float2*>(W1 + (size_t)(p * CC + (tid >> 5)) * (G::kFixed ? HD : a.ldw1) + (tid & 31) * 2);
 
   for (int b0 = 0; b0 < a.B; b0 += 64) {
-    const int nb = min(64, a.B - b0);
+    const int nb = F::nb(a, b0);   // 64 with whole chunks
     bwd32_ids(tid, lane, wave, fr, fq);
     const bool dw_wave = wave >= 8;
     const int v8 = wave & 7;
     // ---- prologue: this chunk's operands, every load issued before the first wait; the replica count
-    // picks the number of hpre registers (uniform switch; more than kMaxRep: the deterministic mode)
+    // picks the number of hpre registers (the form's own count, or a uniform switch; more than kMaxRep: the
+    // deterministic mode)
     Bwd32Chunk ck;
-    if (a.hrep > kMaxRep) bwd32_chunk_issue<0, G>(a, tid, p, py, px, b0, nb, ck);
+    if constexpr (F::kRep > 0) bwd32_chunk_issue<F::kRep, G, F>(a, tid, p, py, px, b0, nb, ck);
+    else if (a.hrep > kMaxRep) bwd32_chunk_issue<0, G, F>(a, tid, p, py, px, b0, nb, ck);
     else switch (a.hrep) {
-      case 1: bwd32_chunk_issue<1, G>(a, tid, p, py, px, b0, nb, ck); break;
-      case 2: bwd32_chunk_issue<2, G>(a, tid, p, py, px, b0, nb, ck); break;
-      case 3: case 4: bwd32_chunk_issue<4, G>(a, tid, p, py, px, b0, nb, ck); break;
-      default: bwd32_chunk_issue<8, G>(a, tid, p, py, px, b0, nb, ck); break;
+      case 1: bwd32_chunk_issue<1, G, F>(a, tid, p, py, px, b0, nb, ck); break;
+      case 2: bwd32_chunk_issue<2, G, F>(a, tid, p, py, px, b0, nb, ck); break;
+      case 3: case 4: bwd32_chunk_issue<4, G, F>(a, tid, p, py, px, b0, nb, ck); break;
+      default: bwd32_chunk_issue<8, G, F>(a, tid, p, py, px, b0, nb, ck); break;
     }
-    stamp(a.stamps, 1);
-    stamp_landed(a.stamps, ck);
-    // the selects of the clamped chunk-0 loads use this iteration's thread indices: they stay here, behind
-    // the chunk's loads, and are not moved up to the loads they would wait for (has_b1: always a.b1 != null)
-    const bool has_b1 = a.b1 && tid >= 0;
+    if constexpr (F::kDiag) {
+      stamp(a.stamps, 1);
+      stamp_landed(a.stamps, ck);
+    }
+    // ragged chunks: the selects of the clamped chunk-0 loads use this iteration's thread indices: they stay
+    // here, behind the chunk's loads, and are not moved up to the loads they would wait for (has_b1: always
+    // a.b1 != null).  Whole chunks have no such selects to hold.
+    const bool has_b1 = F::kWhole ? a.b1 != nullptr : a.b1 && tid >= 0;
     const float4 b1u = has_b1 ? b1v : float4{0.f, 0.f, 0.f, 0.f};
     if (b0 == 0) {
       hl.w2s[(tid >> 4) * W2S + (tid & 15)] = (tid & 15) < a.C ? w2v : 0.f;
       if (tid < 16) hl.b2s[tid] = tid < a.C ? b2v : 0.f;
       *reinterpret_cast<float2*>(W1s + (tid >> 5) * GS32 + (tid & 31) * 2) = w1v;
     }
-    head_stage(a, ck.hv, b1u, tid >> 4, (tid & 15) * 4, nb, hl.hs);
+    head_stage<F>(a, ck.hv, b1u, tid >> 4, (tid & 15) * 4, nb, hl.hs);
     if (tid < 64) hl.labs[tid] = ck.lab;
     *reinterpret_cast<float2*>(Pts + (tid >> 5) * GS32 + (tid & 31) * 2) = ck.ptv;
     if (tid < 256) {
@@ -390,21 +428,21 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
       *reinterpret_cast<uint64_t*>(am + bb * CC + cg * 8) = ck.amv;
     }
     lds_barrier();
-    stamp_fine(a.stamps, 9);
+    if constexpr (F::kDiag) stamp_fine(a.stamps, 9);
     // ---- the head recomputed: G = dH (f32) into LDS, row-major and transposed
     {
       float la = 0.f, ca = 0.f, na = 0.f;   // the head workgroup keeps these: not computed here
-      head_logits_ce16<false>(a, nb, hl, Gs, lane, wave, la, ca, na);   // partial 0 in Gs, free until dH
-      stamp_fine(a.stamps, 11);
-      const f32x4 gh = head_dh(a, nb, hl, lane, wave);
+      head_logits_ce16<false, F>(a, nb, hl, Gs, lane, wave, la, ca, na);   // partial 0 in Gs, free until dH
+      if constexpr (F::kDiag) stamp_fine(a.stamps, 11);
+      const f32x4 gh = head_dh<F>(a, nb, hl, lane, wave);
       const int rt = wave >> 2, j = (wave & 3) * 16 + fr;
 #pragma unroll
       for (int i = 0; i < 4; ++i) Gs[(rt * 16 + fq * 4 + i) * GS32 + j] = gh[i];
       *reinterpret_cast<float4*>(Gts + j * GS32 + rt * 16 + fq * 4) = float4{gh[0], gh[1], gh[2], gh[3]};
-      stamp_fine(a.stamps, 12);
+      if constexpr (F::kDiag) stamp_fine(a.stamps, 12);
     }
     lds_barrier();
-    stamp(a.stamps, 2);
+    if constexpr (F::kDiag) stamp(a.stamps, 2);
 
     // ---- waves 0-7: dP[b][c] = sum_u G[b][u] W1[c][u];  waves 8-15: dW1[c][u] += sum_b P[b][c] G[b][u]
     {
@@ -429,7 +467,7 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
       }
     }
     lds_barrier();
-    stamp(a.stamps, 3);
+    if constexpr (F::kDiag) stamp(a.stamps, 3);
 
     // ---- routing MFMA: k = (b, q), lane group fq = window slot q; wave takes images 4w..4w+3
     {
@@ -448,7 +486,7 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
     }
     lds_barrier();
   }
-  stamp(a.stamps, 4);
+  if constexpr (F::kDiag) stamp(a.stamps, 4);
 
   bwd32_ids(tid, lane, wave, fr, fq);
   const bool dw_wave = wave >= 8;
@@ -489,19 +527,23 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
                    *reinterpret_cast<const float4*>(W1s + row * GS32 + c4));
     xg_push_drain();   // acknowledged before the wave ends
   }
-  stamp(a.stamps, 5);
+  if constexpr (F::kDiag) stamp(a.stamps, 5);
 }
 
-// The runtime-geometry form (the fallback for every shape but 28 x 28) and the specialised one
+// The general form (runtime geometry and counts, stamps: every call the production form does not take) and
+// the production form
+// The production form of the backward: no diagnostics, whole chunks, the 4 hpre replicas train/program.py uses by
+// default
+using ProdForm = BwdForm<false, true, 4>;
 template <int MODE>
 __global__ __launch_bounds__(1024) void convnet32_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  convnet32_bwd_body<MODE, Geo<0, 0>>(a, smem);
+  convnet32_bwd_body<MODE, Geo<0, 0>, BwdFormAny>(a, smem);
 }
 template <int MODE>
 __global__ __launch_bounds__(1024) void convnet32g_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  convnet32_bwd_body<MODE, Geo<kGH, kGW>>(a, smem);
+  convnet32_bwd_body<MODE, Geo<kGH, kGW>, ProdForm>(a, smem);
 }
 
 }  // namespace tde
@@ -509,11 +551,14 @@ __global__ __launch_bounds__(1024) void convnet32g_bwd_kernel(BwdArgs a) {
 using namespace tde;
 using namespace tde::cnet;
 
-// The form the backward's entry point launches: the specialised kernels for 28 x 28 images, the runtime-geometry
-// ones for every other shape.  tde_convnet_f32_runtime_geom(1) forces the runtime form for every shape (the tests
-// compare the two forms on the same inputs); it returns the previous setting.
+// The form the backward's entry point launches: the production kernels for calls that meet every condition of
+// prod_form(), the general ones for every other call.  tde_convnet_f32_runtime_geom(1) forces the general form
+// for every call (the tests compare the two forms on the same inputs); it returns the previous setting.
 static int g_runtime_geom = 0;
 static bool geom_fixed(int H, int W) { return !g_runtime_geom && H == kGH && W == kGW; }
+static bool prod_form(const BwdArgs& a) {
+  return geom_fixed(a.H, a.W) && !a.stamps && a.B > 0 && a.B % 64 == 0 && a.hrep == ProdForm::kRep;
+}
 TDE_API int tde_convnet_f32_runtime_geom(int on) {
   const int prev = g_runtime_geom;
   g_runtime_geom = on ? 1 : 0;
@@ -535,7 +580,8 @@ TDE_API int tde_convnet_fwd_f32(const float* x, const float* wc, const float* bc
   FwdArgs a{x, wc, bc, W1, ldw1, hpre, Pt, ldPt, (uint64_t*)amax, lda, B, H, W, stamps};
   fill_fwd_opt(a, opt, off_wc, off_bc, inc_iter, hrep, hrep_stride);
   const dim3 grid((P + FG - 1) / FG, by);
-  convnet32_fwd_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
+  if (stamps) convnet32_fwd_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
+  else convnet32_fwd_plain_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
   TDE_LAUNCH_CHECK();
   return 0;
 }
@@ -579,7 +625,7 @@ TDE_API int tde_convnet_bwd_f32(const float* x, const void* amax, int lda, const
   }
   const dim3 grid(P + 1);   // one workgroup per pooled position + the head workgroup
   const int mode = !opt ? 0 : (opt->h.kind == kOptSGD ? 1 : 2);
-  if (geom_fixed(H, W)) {
+  if (prod_form(a)) {
     if (mode == 0) convnet32g_bwd_kernel<0><<<grid, 1024, kBwd32Lds, stream>>>(a);
     else if (mode == 1) convnet32g_bwd_kernel<1><<<grid, 1024, kBwd32Lds, stream>>>(a);
     else convnet32g_bwd_kernel<2><<<grid, 1024, kBwd32Lds, stream>>>(a);
