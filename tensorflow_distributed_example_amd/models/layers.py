@@ -579,20 +579,20 @@ class RandomFlip(InputStageLayer):
         return dict(name=self.name, mode=self.mode, seed=self.seed)
 
 
-def _translation_factor(v, what):
+def _translation_factor(v, what, who="RandomTranslation"):
     """A factor f >= 0 (the range [-f, f]) or a pair (lo, hi) with -1 <= lo <= hi <= 1 -> (lo, hi)."""
     if isinstance(v, (tuple, list)):
         if len(v) != 2:
-            raise ValueError(f"RandomTranslation: {what} must be a float or a (lo, hi) pair, got {v!r}")
+            raise ValueError(f"{who}: {what} must be a float or a (lo, hi) pair, got {v!r}")
         lo, hi = float(v[0]), float(v[1])
     elif isinstance(v, (int, float)) and not isinstance(v, bool):
         if v < 0:
-            raise ValueError(f"RandomTranslation: {what} must not be negative, got {v!r}")
+            raise ValueError(f"{who}: {what} must not be negative, got {v!r}")
         lo, hi = -float(v), float(v)
     else:
-        raise ValueError(f"RandomTranslation: {what} must be a float or a (lo, hi) pair, got {v!r}")
+        raise ValueError(f"{who}: {what} must be a float or a (lo, hi) pair, got {v!r}")
     if not (-1.0 <= lo <= hi <= 1.0):
-        raise ValueError(f"RandomTranslation: {what} needs -1 <= lo <= hi <= 1, got {v!r}")
+        raise ValueError(f"{who}: {what} needs -1 <= lo <= hi <= 1, got {v!r}")
     return lo, hi
 
 
@@ -629,9 +629,75 @@ class RandomTranslation(InputStageLayer):
                     fill_value=self.fill_value)
 
 
+class _RandomAffine(InputStageLayer):
+    """What RandomRotation and RandomZoom share: the translation's fill modes and interpolations."""
+    FILL_MODES = RandomTranslation.FILL_MODES
+    INTERPOLATIONS = RandomTranslation.INTERPOLATIONS
+
+    def _sampling(self, fill_mode, interpolation, seed, fill_value):
+        who = type(self).__name__
+        if fill_mode not in self.FILL_MODES:
+            raise ValueError(f"{who}: fill_mode must be one of {self.FILL_MODES}, got {fill_mode!r}")
+        if interpolation not in self.INTERPOLATIONS:
+            raise ValueError(f"{who}: interpolation must be one of {self.INTERPOLATIONS}, got {interpolation!r}")
+        self.fill_mode = fill_mode
+        self.interpolation = interpolation
+        self.seed = None if seed is None else int(seed)
+        self.fill_value = float(fill_value)
+
+
+class RandomRotation(_RandomAffine):
+    """Rotation about the image centre by a fraction of a full turn drawn from ``factor`` (a float f >= 0: the
+    range [-f, f]; or a pair (lo, hi)); a positive value turns the picture counter-clockwise as displayed."""
+    _prefix = "random_rotation"
+
+    def __init__(self, factor, fill_mode="reflect", interpolation="bilinear", seed=None, fill_value=0.0, **kw):
+        super().__init__(**kw)
+        self.factor = tuple(factor) if isinstance(factor, (tuple, list)) else factor
+        self.factor_range = _translation_factor(factor, "factor", "RandomRotation")
+        self._sampling(fill_mode, interpolation, seed, fill_value)
+
+    def aug_layer(self, j):
+        from ..ops import augment as AU
+        return AU.rotate_layer(self.factor_range, self.fill_mode, self.interpolation, self.fill_value, j,
+                               self.resolved_seed(j))
+
+    def get_config(self):
+        return dict(name=self.name, factor=self.factor, fill_mode=self.fill_mode, interpolation=self.interpolation,
+                    seed=self.seed, fill_value=self.fill_value)
+
+
+class RandomZoom(_RandomAffine):
+    """Zoom about the image centre: an axis is scaled by 1 + f with f drawn from its factor's range, positive
+    zooming out and negative in.  ``width_factor=None``: the width takes the height's drawn value (the aspect
+    ratio is kept)."""
+    _prefix = "random_zoom"
+
+    def __init__(self, height_factor, width_factor=None, fill_mode="reflect", interpolation="bilinear", seed=None,
+                 fill_value=0.0, **kw):
+        super().__init__(**kw)
+        self.height_factor = tuple(height_factor) if isinstance(height_factor, (tuple, list)) else height_factor
+        self.width_factor = tuple(width_factor) if isinstance(width_factor, (tuple, list)) else width_factor
+        self.height_range = _translation_factor(height_factor, "height_factor", "RandomZoom")
+        self.width_range = None if width_factor is None else _translation_factor(width_factor, "width_factor",
+                                                                                 "RandomZoom")
+        self._sampling(fill_mode, interpolation, seed, fill_value)
+
+    def aug_layer(self, j):
+        from ..ops import augment as AU
+        return AU.zoom_layer(self.height_range, self.width_range, self.fill_mode, self.interpolation, self.fill_value,
+                             j, self.resolved_seed(j))
+
+    def get_config(self):
+        return dict(name=self.name, height_factor=self.height_factor, width_factor=self.width_factor,
+                    fill_mode=self.fill_mode, interpolation=self.interpolation, seed=self.seed,
+                    fill_value=self.fill_value)
+
+
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
-                                         Dropout, BatchNormalization, Add, RandomFlip, RandomTranslation]}
+                                         Dropout, BatchNormalization, Add, RandomFlip, RandomTranslation,
+                                         RandomRotation, RandomZoom]}
 
 
 def from_config(cls_name, cfg):

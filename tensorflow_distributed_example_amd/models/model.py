@@ -105,7 +105,7 @@ class Model:
 
     @property
     def input_stage(self):
-        """The RandomFlip / RandomTranslation layers in front of the model, in model order."""
+        """The random image layers (``InputStageLayer``s) in front of the model, in model order."""
         return self._split_input_stage()[0]
 
     @property

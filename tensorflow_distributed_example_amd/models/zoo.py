@@ -99,7 +99,7 @@ def mnist_mlp(name=None):
 
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
-    ``stage``: a list of RandomFlip / RandomTranslation layers.  The input becomes the image itself: a model
+    ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model
     that starts by reshaping flat rows (``mnist_bn_cnn``) takes its Reshape target as the input shape.  The
     layers of ``stage`` become the new model's own (the first one is given the model's input shape): pass
     fresh layers, not ones that stand in another model."""
