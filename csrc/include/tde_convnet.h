@@ -20,6 +20,33 @@ constexpr int CC = 32;   // conv filters
 constexpr int HD = 64;   // Dense units
 constexpr int NW = 16;   // waves of a backward workgroup
 
+// Which workgroup of a launch does which piece of the step (float32 kernels).  Workgroups are dealt round-robin
+// over the 8 XCDs, so ids congruent mod 8 share an XCD and its L2 (observed, not promised: a wrong guess is
+// slower, never wrong).  The maps put the workgroups that hand W1 rows, Pt rows and argmax words to each
+// other between the two launches on ids of one class: in every full run of 8 groups (32 pooled positions) group g's
+// forward tiles and the backward workgroups of its positions 4g..4g+3 all have ids = g (mod 8).  The last,
+// partial run keeps the launch order (forward: group fastest; backward: position = id).
+// fwd_slot / bwd_slot are the maps; the *_runs forms take the number of full runs (0: the identity maps,
+// tde_convnet_f32_identity_slots) so a kernel gets it as an argument.
+struct FwdSlot { int g, y; };   // position group, image tile
+__host__ __device__ constexpr FwdSlot fwd_slot_runs(int id, int groups, int tiles, int full) {
+  const int run = 8 * tiles;
+  if (id < full * run) {
+    const int r = id / run, rem = id - r * run;
+    return FwdSlot{8 * r + (rem & 7), rem >> 3};
+  }
+  const int k = id - full * run, rest = groups - 8 * full;
+  return FwdSlot{8 * full + k % rest, k / rest};
+}
+__host__ __device__ constexpr FwdSlot fwd_slot(int id, int groups, int tiles) {
+  return fwd_slot_runs(id, groups, tiles, groups / 8);
+}
+// backward: id 32r + 8j + c is position 4 (8r + c) + j; the head workgroup (id P) is not mapped
+__host__ __device__ constexpr int bwd_slot_runs(int id, int full) {
+  return id < 32 * full ? (id & ~31) + 4 * (id & 7) + ((id >> 3) & 3) : id;
+}
+__host__ __device__ constexpr int bwd_slot(int id, int P) { return bwd_slot_runs(id, P / 32); }
+
 struct FwdArgs {
   const float* x; const float* wc; const float* bc;
   const void* W1; int ldw1;          // bf16 shadow ([K][HD] rows or [HD][K]) | f32 master [K][HD]
@@ -45,6 +72,8 @@ struct FwdArgs {
   const float *hsrc_w2, *hsrc_b2, *hsrc_b1;
   float* hsnap;                      // [64 b1 | 64*hC W2 | hC b2]
   int hC;
+  // float32 kernels: 1-D grid of groups * tiles workgroups, placed by fwd_slot_runs(id, groups, tiles, slot_full)
+  int groups, tiles, slot_full;
 };
 
 // Fused step: one forward workgroup copies the head variables into the snapshot the backward reads.
@@ -285,6 +314,7 @@ struct BwdArgs {
   FlatApply commit;                  // the previous step's deferred conv update (head workgroup, while *pend)
   int* pend_set;                     // := 1: this step's conv update is deferred
   XgPush push;                       // MODE 0, nranks > 0: dW1 goes to the xGMI owners (fused DP exchange)
+  int slot_full;                     // float32 kernels: workgroup id -> position by bwd_slot_runs(id, slot_full)
 };
 
 // What a form of the float32 backward knows at compile time, next to its image geometry (convnet_f32.hip: Geo).
@@ -781,7 +811,10 @@ __device__ __forceinline__ void head_workgroup(const BwdArgs& a, const HeadLds& 
 
 // Reduces the routing accumulators (conv weight / bias gradients: [tap 0..8 | bias 9][CC]) of the
 // 16 waves through LDS (red: [NW][16][CC] f32) and adds them into dwc / dbc.
-__device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 accr[2], float* red, int lane, int wave) {
+// wg: the workgroup's place in the partials and among the replicas: its pooled position (the block id, where the
+// two are the same), so neither the order of the deterministic sum nor a replica's addends depend on placement.
+__device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 accr[2], float* red, int lane, int wave,
+                                                 int wg) {
   const int fr = lane & 15, fq = lane >> 4, tid = threadIdx.x;
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
@@ -793,11 +826,11 @@ __device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 a
     float s = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) s += red[((size_t)w * 16 + tap) * CC + c];
-    if (a.cpart) a.cpart[(size_t)blockIdx.x * 10 * CC + tid] = s;   // deterministic: summed by cgrad_reduce
+    if (a.cpart) a.cpart[(size_t)wg * 10 * CC + tid] = s;   // deterministic: summed by cgrad_reduce
     else {
       // replicas spread the adds of the ~170 workgroups over crep addresses per value (the contention
       // of 170 same-address float atomics cost ~4 us of the MNIST-CNN backward)
-      const long long ro = a.crep > 1 ? (long long)(blockIdx.x % a.crep) * a.crep_stride : 0;
+      const long long ro = a.crep > 1 ? (long long)(wg % a.crep) * a.crep_stride : 0;
       if (tap < 9) {
         if (a.dwc) atomicAdd(a.dwc + ro + tap * CC + c, s);
       } else if (a.dbc) {
@@ -806,6 +839,20 @@ __device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 a
     }
   }
 }
+__device__ __forceinline__ void conv_grad_reduce(const BwdArgs& a, const f32x4 accr[2], float* red, int lane, int wave) {
+  conv_grad_reduce(a, accr, red, lane, wave, (int)blockIdx.x);
+}
+
+// The XCD a workgroup runs on (HW_REG_XCC_ID, bits 3:0) into stamp slot `slot` of the workgroup, as id + 1 so that
+// a slot nobody wrote stays 0 (diagnostic runs: bench/micro.py's placement table).
+__device__ __forceinline__ void stamp_xcc(long long* st, int slot) {
+  if (st && threadIdx.x == 0) {
+    const int blk = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    // s_getreg_b32 hwreg(HW_REG_XCC_ID = 20, offset 0, size 4)
+    st[(size_t)blk * kMaxStamps + slot] = 1 + (long long)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xf);
+  }
+}
+constexpr int kXccSlot = 6;   // free in both float32 kernels' first bank
 
 }  // namespace cnet
 }  // namespace tde

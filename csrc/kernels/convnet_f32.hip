@@ -27,6 +27,13 @@
 // offset shifts every lane's bank alike), the ds_read_b128 lane groups hit disjoint banks (searched
 // exhaustively over strides and per-group rotations).
 //
+// Placement: every operand handed from one launch to the other (the W1 rows the backward rewrites and the next
+// forward reads; the Pt rows and argmax words the forward stores and the backward reads) is written by plain
+// stores, which stay in the writing XCD's L2.  Both launches have a 1-D grid whose workgroup ids are mapped
+// (tde_convnet.h: fwd_slot, bwd_slot) so that writer and reader of those lines have ids of one class mod 8, that
+// is, run on one XCD (profiles/xcd_handoff/NOTES.md: measured placement, eager and in a graph).  Only speed
+// depends on it.  tde_convnet_f32_identity_slots(1) forces the identity maps.
+//
 // Each launch has a production form and a general one, picked by the entry points:
 //   forward   convnet32_fwd_plain_kernel: no stamp buffer given (every training and inference step);
 //             convnet32_fwd_kernel: the same body with its five phase stamps, for calls with a stamp buffer.
@@ -119,14 +126,19 @@ __device__ __forceinline__ void convnet32_fwd_body(const FwdArgs& a, unsigned ch
   int pendv;
   long long iterv;
   conv_flags_issue(a, pendv, iterv);
-  if constexpr (DIAG) stamp(a.stamps, 0);
+  if constexpr (DIAG) {
+    stamp(a.stamps, 0);
+    stamp_xcc(a.stamps, kXccSlot);
+  }
   if (a.inc_iter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(a.inc_iter, 1ull);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
   const int W = a.W, H = a.H;
   const int Wp = (W - 2) / 2, Hp = (H - 2) / 2, P = Hp * Wp;
-  const int p0 = blockIdx.x * FG;
-  const int b0 = blockIdx.y * FB;
+  // 1-D grid: this workgroup's position group and image tile (tde_convnet.h: fwd_slot)
+  const FwdSlot sl = fwd_slot_runs((int)blockIdx.x, a.groups, a.tiles, a.slot_full);
+  const int p0 = sl.g * FG;
+  const int b0 = sl.y * FB;
   const int py0 = p0 / Wp;   // FG <= Wp (host check): the group's positions lie in pooled rows py0, py0 + 1
   const int nrows = min(XR, H - 2 * py0);
   const float* W1 = reinterpret_cast<const float*>(a.W1);
@@ -201,7 +213,8 @@ __device__ __forceinline__ void convnet32_fwd_body(const FwdArgs& a, unsigned ch
   // ---- phase 2: hpre[16 x 64] += As(16 x FG*32) . W1(FG*32 x 64) on the f32 MFMA; wave = column tile nt,
   // one accumulator per position (independent chains keep the pipe issuing), summed before the adds:
   // the FG positions' split-K partial sums meet in registers, not in memory
-  float* const hrow = a.hpre + (size_t)(blockIdx.x % a.hrep) * a.hrep_stride;
+  // the replica is the group's, wherever its workgroups run: every replica's addends are the same under any map
+  float* const hrow = a.hpre + (size_t)(sl.g % a.hrep) * a.hrep_stride;
   f32x4 acc[FG];
 #pragma unroll
   for (int ks = 0; ks < FG; ++ks) acc[ks] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -338,7 +351,10 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
   if (MODE == 2) t_it = *a.iterations;
   // workgroups of the launch: read once, ahead of the first branch (a scalar load); a constant in the fixed form
   const unsigned nwg = G::kFixed ? ((kGH - 2) / 2) * ((kGW - 2) / 2) + 1 : gridDim.x;
-  if constexpr (F::kDiag) stamp(a.stamps, 0);
+  if constexpr (F::kDiag) {
+    stamp(a.stamps, 0);
+    stamp_xcc(a.stamps, kXccSlot);
+  }
   const int W = G::W(a);
   int tid, lane, wave, fr, fq;
   bwd32_ids(tid, lane, wave, fr, fq);
@@ -362,7 +378,8 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
   }
 
   const int Wp = (W - 2) / 2;
-  const int p = blockIdx.x;            // one pooled position per workgroup (grid = P + 1)
+  // one pooled position per workgroup (grid = P + 1), placed by tde_convnet.h: bwd_slot
+  const int p = bwd_slot_runs((int)blockIdx.x, a.slot_full);
   const int py = p / Wp, px = p - py * Wp;
   // no Dense(64) bias: the load reads hpre's first row (same alignment) and counts as 0
   const float4 b1v = *reinterpret_cast<const float4*>((a.b1 ? a.b1 : a.hpre) + (tid & 15) * 4);
@@ -517,7 +534,7 @@ __device__ __forceinline__ void convnet32_bwd_body(const BwdArgs& a, unsigned ch
       for (int r = 0; r < 4; ++r) a.dW1[(size_t)(p * CC + rt * 16 + fq * 4 + r) * HD + col] = accw[r];
     }
   }
-  conv_grad_reduce(a, accr, dps, lane, wave);   // its barrier also publishes the W1s staging
+  conv_grad_reduce(a, accr, dps, lane, wave, p);   // its barrier also publishes the W1s staging
   if (MODE == 0 && a.push.nranks > 0 && tid < CC * HD / 4) {
     // the rows go straight into the owners' contribution areas of the all-reduce call that follows this
     // launch (its parity from the completed-calls count); the bucket offset is a multiple of 4 (host check)
@@ -565,6 +582,34 @@ TDE_API int tde_convnet_f32_runtime_geom(int on) {
   return prev;
 }
 
+// The placement maps of both launches (tde_convnet.h: fwd_slot, bwd_slot).  tde_convnet_f32_identity_slots(1)
+// forces the identity maps (forward: group fastest, backward: position = id) for every call, for tests and A/B
+// timing; it returns the previous setting.
+static int g_identity_slots = 0;
+static int fwd_full_runs(int groups) { return g_identity_slots ? 0 : groups / 8; }
+static int bwd_full_runs(int P) { return g_identity_slots ? 0 : P / 32; }
+TDE_API int tde_convnet_f32_identity_slots(int on) {
+  const int prev = g_identity_slots;
+  g_identity_slots = on ? 1 : 0;
+  return prev;
+}
+// The whole map in effect, for checks without a GPU.  kind 0: the forward's, a = groups, b = tiles,
+// out[2 id] = group, out[2 id + 1] = tile of workgroup id < a * b; kind 1: the backward's, a = P,
+// out[id] = position of workgroup id < P (the head workgroup, id P, is not mapped).  Returns the workgroup count.
+TDE_API int tde_convnet_slot_map(int kind, int a, int b, int* out) {
+  if (!out || a < 1 || (kind == 0 && b < 1) || (kind != 0 && kind != 1)) return -1;
+  if (kind == 0) {
+    for (int id = 0; id < a * b; ++id) {
+      const FwdSlot s = fwd_slot_runs(id, a, b, fwd_full_runs(a));
+      out[2 * id] = s.g;
+      out[2 * id + 1] = s.y;
+    }
+    return a * b;
+  }
+  for (int id = 0; id < a; ++id) out[id] = bwd_slot_runs(id, bwd_full_runs(a));
+  return a;
+}
+
 // Float32 forward: W1 is the f32 master Dense(64) kernel [K][64] (ldw1 = 64), Pt f32 [K][ldPt].
 // opt / off_wc / off_bc / inc_iter / hrep as tde_convnet_fwd.
 TDE_API int tde_convnet_fwd_f32(const float* x, const float* wc, const float* bc, const float* W1, int ldw1,
@@ -579,7 +624,10 @@ TDE_API int tde_convnet_fwd_f32(const float* x, const float* wc, const float* bc
   const int by = ((Pt && ldPt > B ? ldPt : B) + FB - 1) / FB;
   FwdArgs a{x, wc, bc, W1, ldw1, hpre, Pt, ldPt, (uint64_t*)amax, lda, B, H, W, stamps};
   fill_fwd_opt(a, opt, off_wc, off_bc, inc_iter, hrep, hrep_stride);
-  const dim3 grid((P + FG - 1) / FG, by);
+  a.groups = (P + FG - 1) / FG;
+  a.tiles = by;
+  a.slot_full = fwd_full_runs(a.groups);
+  const dim3 grid(a.groups * a.tiles);
   if (stamps) convnet32_fwd_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
   else convnet32_fwd_plain_kernel<<<grid, 256, kFwd32Lds, stream>>>(a);
   TDE_LAUNCH_CHECK();
@@ -613,6 +661,7 @@ TDE_API int tde_convnet_bwd_f32(const float* x, const void* amax, int lda, const
     a.crep_stride = crep_stride;
   }
   const int P = ((H - 2) / 2) * ((W - 2) / 2);
+  a.slot_full = bwd_full_runs(P);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)convnet32_bwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kBwd32Lds);
