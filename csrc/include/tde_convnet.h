@@ -275,6 +275,49 @@ __device__ __forceinline__ void conv_pool8(const float* xb, int W, const ConvW8&
   }
 }
 
+// The 4-channel form (the float32 forward: 8 waves, wave w owns channels 4w..4w+3): the same expression in
+// the same order per (image, position, channel) as conv_pool8, so every value and every argmax byte is the
+// one the 8-channel form computes.  packed = 4 argmax bytes, channel cc at bit 8 * cc.
+struct ConvW4 {
+  float4 w[9], b;
+  __device__ __forceinline__ void load(const float* wcs, int c0) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) w[t] = *reinterpret_cast<const float4*>(wcs + t * CC + c0);
+    b = *reinterpret_cast<const float4*>(wcs + 9 * CC + c0);
+  }
+};
+__device__ __forceinline__ void conv_pool4(const float* xb, int W, const ConvW4& cw, float out[4], uint32_t& packed) {
+  float patch[16];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float2 u = *reinterpret_cast<const float2*>(xb + r * W);
+    const float2 v = *reinterpret_cast<const float2*>(xb + r * W + 2);
+    patch[r * 4 + 0] = u.x; patch[r * 4 + 1] = u.y; patch[r * 4 + 2] = v.x; patch[r * 4 + 3] = v.y;
+  }
+  packed = 0;
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) {
+    float wt[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) wt[t] = f4get(cw.w[t], cc);
+    const float bcv = f4get(cw.b, cc);
+    float best = -3.0e38f;
+    int bi = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int dy = q >> 1, dx = q & 1;
+      float z = bcv;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) z = fmaf(patch[(dy + ky) * 4 + dx + kx], wt[ky * 3 + kx], z);
+      if (z > best) { best = z; bi = q; }
+    }
+    out[cc] = fmaxf(best, 0.f);
+    packed |= (best > 0.f ? (unsigned)bi : 0xFFu) << (8 * cc);
+  }
+}
+
 // Backward of the trunk with the classifier head fused in (the head is
 // the same math as head.hip): per 64-image chunk every workgroup recomputes the head from the
 // Dense(64) pre-activation (16 KB f32): h = ReLU(hpre + b1) -> logits = h . W2 + b2 (exact f32
