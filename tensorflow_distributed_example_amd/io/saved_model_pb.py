@@ -7,7 +7,7 @@ tensor.proto, tensor_shape.proto, versions.proto).
 One MetaGraphDef tagged ``serve``:
 * GraphDef — the inference graph with TensorFlow's standard ops: ``Placeholder`` for the serving input,
   resource variables (``VarHandleOp`` + ``ReadVariableOp``, shared names = the TF1 variable names of the
-  exported TensorBundle), ``Reshape`` / ``Conv2D`` / ``BiasAdd`` / ``Relu`` / ``Tanh`` / ``Sigmoid`` /
+  exported TensorBundle), ``Reshape`` / ``Conv2D`` / ``DepthwiseConv2dNative`` / ``BiasAdd`` / ``Relu`` / ``Tanh`` / ``Sigmoid`` /
   ``MaxPool`` / ``AvgPool`` / ``FusedBatchNormV3`` (4-D, ``is_training=false``) or the Keras 2-D batchnorm arithmetic / ``MatMul`` /
   ``Softmax`` / ``AddV2`` / ``Mean`` / ``Pad`` / ``Identity`` (Dropout at inference);
 * the ``save/`` subgraph (``SaveV2`` / ``RestoreV2`` + ``AssignVariableOp`` → ``save/restore_all``) and a
@@ -167,6 +167,22 @@ def build_graph(model, input_name="Placeholder", input_shape=None):
                        strides=A.ints([1, layer.strides[0], layer.strides[1], 1]),
                        padding=A.s(layer.padding.upper()), data_format=A.s("NHWC"), dilations=A.ints([1, 1, 1, 1]),
                        use_cudnn_on_gpu=A.b(True), explicit_paddings=A.empty_list(), **_float_attrs())
+            if layer.use_bias:
+                y = g.node(f"{nm}/BiasAdd", "BiasAdd", [y, read(f"{nm}/bias", f"{nm}/BiasAdd")],
+                           data_format=A.s("NHWC"), **_float_attrs())
+            y = _activation(g, nm, y, layer.activation)
+        elif isinstance(layer, L.DepthwiseConv2D):   # and SeparableConv2D: + its 1x1 Conv2D
+            conv = dict(padding=A.s(layer.padding.upper()), data_format=A.s("NHWC"), dilations=A.ints([1, 1, 1, 1]),
+                        explicit_paddings=A.empty_list(), **_float_attrs())
+            sep = isinstance(layer, L.SeparableConv2D)
+            scope = f"{nm}/separable_conv2d" if sep else nm
+            y = g.node(f"{scope}/depthwise", "DepthwiseConv2dNative",
+                       [x, read(f"{nm}/depthwise_kernel", f"{scope}/depthwise")],
+                       strides=A.ints([1, layer.strides[0], layer.strides[1], 1]), **conv)
+            if sep:
+                conv["padding"] = A.s("VALID")
+                y = g.node(scope, "Conv2D", [y, read(f"{nm}/pointwise_kernel", scope)], strides=A.ints([1, 1, 1, 1]),
+                           use_cudnn_on_gpu=A.b(True), **conv)
             if layer.use_bias:
                 y = g.node(f"{nm}/BiasAdd", "BiasAdd", [y, read(f"{nm}/bias", f"{nm}/BiasAdd")],
                            data_format=A.s("NHWC"), **_float_attrs())
@@ -367,6 +383,8 @@ def run_graph(graph_nodes, feeds: dict, variables: dict, fetch: str):
             return xs[0].reshape([int(d) for d in xs[1]])
         if op == "Conv2D":
             return _conv2d(xs[0], xs[1], at["strides"][1:3], at["padding"])
+        if op == "DepthwiseConv2dNative":
+            return _depthwise_conv2d(xs[0], xs[1], at["strides"][1:3], at["padding"])
         if op == "BiasAdd":
             return xs[0] + xs[1]
         if op == "Relu":
@@ -424,6 +442,23 @@ def _conv2d(x, w, strides, padding):
             patch = x[:, i: i + sh * (Ho - 1) + 1: sh, j: j + sw * (Wo - 1) + 1: sw, :]
             out += patch @ w[i, j]
     return out
+
+
+def _depthwise_conv2d(x, w, strides, padding):
+    """TF DepthwiseConv2dNative: filter [kh, kw, C, dm], output channel c*dm + m."""
+    B, H, W, C = x.shape
+    kh, kw, _, dm = w.shape
+    sh, sw = strides
+    if padding == "SAME":
+        (pt, pb), (pl, pr) = _same_pads(H, kh, sh), _same_pads(W, kw, sw)
+        x = np.pad(x, [(0, 0), (pt, pb), (pl, pr), (0, 0)])
+    Ho, Wo = (x.shape[1] - kh) // sh + 1, (x.shape[2] - kw) // sw + 1
+    out = np.zeros((B, Ho, Wo, C, dm))
+    for i in range(kh):
+        for j in range(kw):
+            patch = x[:, i: i + sh * (Ho - 1) + 1: sh, j: j + sw * (Wo - 1) + 1: sw, :]
+            out += patch[..., None] * w[i, j]
+    return out.reshape(B, Ho, Wo, C * dm)
 
 
 def _maxpool(x, ksize, strides, padding):

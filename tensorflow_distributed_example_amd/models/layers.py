@@ -268,6 +268,114 @@ class Conv2D(Layer):
                     **_reg_config(self, "kernel_regularizer", "bias_regularizer"))
 
 
+def _depthwise_ref(x, kernel, strides, pads):
+    """NHWC depthwise convolution of x with a Keras depthwise_kernel [KH, KW, C, dm] in torch ops: a grouped
+    conv (groups = C) whose output channel c*dm + m is filter m of input channel c."""
+    (pt, pb), (pl, pr) = pads
+    kh, kw, C, dm = kernel.shape
+    xc = x.permute(0, 3, 1, 2)
+    if pt or pb or pl or pr:
+        xc = F.pad(xc, (pl, pr, pt, pb))
+    k = kernel.reshape(kh, kw, 1, C * dm).permute(3, 2, 0, 1)
+    return F.conv2d(xc, k, stride=strides, groups=C).permute(0, 2, 3, 1)
+
+
+class DepthwiseConv2D(Layer):
+    """Keras ``DepthwiseConv2D``: every input channel convolved with its own ``depth_multiplier`` filters
+    (weights ``depthwise_kernel`` [KH, KW, C, dm], ``bias`` [C*dm]).  On the GPU: csrc/kernels/depthwise.hip.
+    Not a ``Conv2D`` subclass: the plan matchers tell the layers apart by type."""
+    _prefix = "depthwise_conv2d"
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, activation=None,
+                 use_bias=True, depthwise_initializer="glorot_uniform", bias_initializer="zeros",
+                 data_format=None, dilation_rate=(1, 1), depthwise_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(**kw)
+        if data_format not in (None, "channels_last"):
+            raise ValueError("only channels_last is supported (Keras default)")
+        if _tuple2(dilation_rate) != (1, 1):
+            raise ValueError("dilation is not supported")
+        self.kernel_size = _tuple2(kernel_size)
+        self.strides = _tuple2(strides)
+        self.padding = padding.lower()
+        if self.padding not in ("valid", "same"):
+            raise ValueError(padding)
+        self.depth_multiplier = int(depth_multiplier)
+        if self.depth_multiplier < 1:
+            raise ValueError(f"depth_multiplier must be positive, got {depth_multiplier}")
+        self.filters = None   # output channels: C * depth_multiplier, known at build
+        self.activation = get_activation(activation)
+        self.use_bias = use_bias
+        self.depthwise_initializer = depthwise_initializer
+        self.bias_initializer = bias_initializer
+        self.depthwise_regularizer = regularizers.get(depthwise_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
+
+    pads = Conv2D.pads
+    compute_output_shape = Conv2D.compute_output_shape
+
+    def _add_depthwise(self, cin):
+        kh, kw = self.kernel_size
+        self.add_weight("depthwise_kernel", (kh, kw, cin, self.depth_multiplier), self.depthwise_initializer,
+                        regularizer=self.depthwise_regularizer)
+
+    def build(self, input_shape):
+        self.filters = input_shape[-1] * self.depth_multiplier
+        self._add_depthwise(input_shape[-1])
+        if self.use_bias:
+            self.add_weight("bias", (self.filters,), self.bias_initializer, regularizer=self.bias_regularizer)
+        self.built = True
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        y = _depthwise_ref(x, W["depthwise_kernel"], self.strides, self.pads(x.shape[1:]))
+        if self.use_bias:
+            y = y + W["bias"]
+        return apply_activation(y, self.activation)
+
+    def get_config(self):
+        return dict(name=self.name, kernel_size=self.kernel_size, strides=self.strides, padding=self.padding,
+                    depth_multiplier=self.depth_multiplier, activation=self.activation, use_bias=self.use_bias,
+                    **_reg_config(self, "depthwise_regularizer", "bias_regularizer"))
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """Keras ``SeparableConv2D``: a depthwise convolution, then a 1x1 convolution to ``filters`` channels
+    (weights ``depthwise_kernel``, ``pointwise_kernel`` [1, 1, C*dm, filters], ``bias`` [filters]); the bias
+    and the activation come after the pointwise step only."""
+    _prefix = "separable_conv2d"
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, activation=None,
+                 use_bias=True, depthwise_initializer="glorot_uniform", pointwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", data_format=None, dilation_rate=(1, 1), depthwise_regularizer=None,
+                 pointwise_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(kernel_size, strides=strides, padding=padding, depth_multiplier=depth_multiplier,
+                         activation=activation, use_bias=use_bias, depthwise_initializer=depthwise_initializer,
+                         bias_initializer=bias_initializer, data_format=data_format, dilation_rate=dilation_rate,
+                         depthwise_regularizer=depthwise_regularizer, bias_regularizer=bias_regularizer, **kw)
+        self.filters = int(filters)
+        self.pointwise_initializer = pointwise_initializer
+        self.pointwise_regularizer = regularizers.get(pointwise_regularizer)
+
+    def build(self, input_shape):
+        cin = input_shape[-1]
+        self._add_depthwise(cin)
+        self.add_weight("pointwise_kernel", (1, 1, cin * self.depth_multiplier, self.filters),
+                        self.pointwise_initializer, regularizer=self.pointwise_regularizer)
+        if self.use_bias:
+            self.add_weight("bias", (self.filters,), self.bias_initializer, regularizer=self.bias_regularizer)
+        self.built = True
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        y = _depthwise_ref(x, W["depthwise_kernel"], self.strides, self.pads(x.shape[1:]))
+        y = y @ W["pointwise_kernel"][0, 0]
+        if self.use_bias:
+            y = y + W["bias"]
+        return apply_activation(y, self.activation)
+
+    def get_config(self):
+        return dict(filters=self.filters, **super().get_config(),
+                    **_reg_config(self, "pointwise_regularizer"))
+
+
 class Dense(Layer):
     _prefix = "dense"
 
@@ -694,7 +802,7 @@ class RandomZoom(_RandomAffine):
                     fill_value=self.fill_value)
 
 
-LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, Dense, MaxPooling2D, AveragePooling2D,
+LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, Add, RandomFlip, RandomTranslation,
                                          RandomRotation, RandomZoom]}

@@ -32,6 +32,11 @@ N.register_hip({
     "tde_gap32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tde_pad32": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tde_xent32": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
+    # csrc/kernels/depthwise.hip
+    "tde_dwconv32_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),          # x, w, bias, relu, y, geo, stream
+    "tde_dwconv32_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),        # dy, y, w, dx, accum, geo, stream
+    "tde_dwconv32_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),  # x, dy, y, dW, db, part, geo, stream
+    "tde_dwconv32_splits": (_i, [_vp]),
 })
 
 _NODROP = DropSpec()
@@ -174,6 +179,71 @@ def dense_wgrad(x, dy, dW, rows, part=None):
     _f32(dy, rows * fout, "dense_wgrad dy")
     s = wgrad_splits(fin, fout, rows) if part is not None else 1
     igemm32(x, fin, A_COLM, dy, fout, B_KN, fin, fout, rows, dW, fout, splits=s, part=part)
+
+
+# ---------------------------------------------------------------- DepthwiseConv2D (csrc/kernels/depthwise.hip)
+DW_MAX_K, DW_MAX_STRIDE, DW_MAX_DM = 7, 4, 8
+
+
+def dw_check(g: ConvGeom, what):
+    """The supported range of the depthwise kernels; returns (x, y, w) element counts.  Co = C * dm."""
+    _req(min(g.B, g.H, g.W, g.C, g.Ho, g.Wo, g.Co) >= 1, f"{what}: empty geometry {g}")
+    _req(1 <= g.KH <= DW_MAX_K and 1 <= g.KW <= DW_MAX_K, f"{what}: kernel {g.KH}x{g.KW} (at most 7x7)")
+    _req(1 <= g.sh <= DW_MAX_STRIDE and 1 <= g.sw <= DW_MAX_STRIDE, f"{what}: strides ({g.sh}, {g.sw}) (at most 4)")
+    _req(g.Co % g.C == 0 and g.Co // g.C <= DW_MAX_DM, f"{what}: depth multiplier {g.Co / g.C:g} (an integer <= 8)")
+    _req(0 <= g.pt < g.KH and 0 <= g.pl < g.KW, f"{what}: pads ({g.pt}, {g.pl})")
+    _req((g.Ho - 1) * g.sh - g.pt < g.H and (g.Wo - 1) * g.sw - g.pl < g.W, f"{what}: output extent past the input")
+    return g.B * g.H * g.W * g.C, g.B * g.Ho * g.Wo * g.Co, g.KH * g.KW * g.Co
+
+
+def dw_splits(g: ConvGeom):
+    """Pixel splits of the depthwise weight gradient (the kernel library's own rule: one source of truth)."""
+    dw_check(g, "dw_splits")
+    return int(N.hip().tde_dwconv32_splits(g.carray()))
+
+
+def dw_part_elems(g: ConvGeom):
+    """f32 elements of the per-split partial rows [splits][KH*KW*Co + Co] of ``dw_wgrad``."""
+    return dw_splits(g) * (g.KH * g.KW * g.Co + g.Co)
+
+
+def dw_fwd(x, w, y, g: ConvGeom, bias=None, relu=False):
+    """y[B,Ho,Wo,C*dm] = act(bias + depthwise_conv(x, w)); w the Keras depthwise_kernel [KH,KW,C,dm] master."""
+    nx, ny, nw = dw_check(g, "dw_fwd")
+    _f32(x, nx, "dw_fwd x")
+    _f32(w, nw, "dw_fwd w")
+    _f32(y, ny, "dw_fwd y")
+    if bias is not None:
+        _f32(bias, g.Co, "dw_fwd bias")
+    N.check(N.hip().tde_dwconv32_fwd(_P(x), _P(w), _P(bias), int(relu), _P(y), g.carray(), _s()), "tde_dwconv32_fwd")
+
+
+def dw_dgrad(dy, w, dx, g: ConvGeom, y=None, accum=False):
+    """dx (+)= the input gradient of dy * (y > 0) (``y``: the layer's ReLU output; None: linear)."""
+    nx, ny, nw = dw_check(g, "dw_dgrad")
+    _f32(dy, ny, "dw_dgrad dy")
+    _f32(w, nw, "dw_dgrad w")
+    _f32(dx, nx, "dw_dgrad dx")
+    if y is not None:
+        _f32(y, ny, "dw_dgrad y")
+    N.check(N.hip().tde_dwconv32_dgrad(_P(dy), _P(y), _P(w), _P(dx), int(accum), g.carray(), _s()),
+            "tde_dwconv32_dgrad")
+
+
+def dw_wgrad(x, dy, dW, g: ConvGeom, part, y=None, db=None):
+    """dW[KH,KW,C,dm] = sum over pixels x . dy * (y > 0), db[Co] = sum of that dy; per-split partials in ``part``
+    (``dw_part_elems``), summed in split order: bitwise reproducible."""
+    nx, ny, nw = dw_check(g, "dw_wgrad")
+    _f32(x, nx, "dw_wgrad x")
+    _f32(dy, ny, "dw_wgrad dy")
+    _f32(dW, nw, "dw_wgrad dW")
+    _f32(part, dw_part_elems(g), "dw_wgrad partials")
+    if y is not None:
+        _f32(y, ny, "dw_wgrad y")
+    if db is not None:
+        _f32(db, g.Co, "dw_wgrad db")
+    N.check(N.hip().tde_dwconv32_wgrad(_P(x), _P(dy), _P(y), _P(dW), _P(db), _P(part), g.carray(), _s()),
+            "tde_dwconv32_wgrad")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

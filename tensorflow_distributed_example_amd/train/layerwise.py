@@ -183,7 +183,8 @@ class LayerwisePlan(PG.ReplicaPlan):
 
         # pass 1: decide GEMM -> BN statistics fusion
         for i, (layer, ins, out) in enumerate(nodes):
-            if isinstance(layer, (L.Conv2D, L.Dense)) and i != n_nodes - 1 and layer.activation is None:
+            if (isinstance(layer, (L.Conv2D, L.Dense, L.SeparableConv2D)) and i != n_nodes - 1
+                    and layer.activation is None):
                 c = single(T[out])
                 if c is not None and isinstance(c[0], L.BatchNormalization):
                     bn_fed[nodes.index(c)] = i
@@ -217,6 +218,20 @@ class LayerwisePlan(PG.ReplicaPlan):
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r}")
                 stats = i in {v: k for k, v in bn_fed.items()}
                 stages.append(_Gemm(self, layer, tin[0], tout, stats))
+                continue
+            if isinstance(layer, L.SeparableConv2D):
+                # depthwise step (no bias, no activation) into an internal tensor, then the 1x1 GEMM stage on
+                # pointwise_kernel with the layer's bias / activation (and everything a Conv2D stage fuses)
+                if layer.activation not in (None, "relu"):
+                    raise Unsupported(f"{layer.name}: activation {layer.activation!r}")
+                mid = _T(max(T) + 1, tout.shape[:2] + (tin[0].C * layer.depth_multiplier,))
+                mid.producer, mid.consumers = i, [i]
+                T[mid.id] = mid
+                stages.append(_Depthwise(self, layer, tin[0], mid, head=False))
+                stages.append(_Gemm(self, layer, mid, tout, i in bn_fed.values(), pointwise=True))
+                continue
+            if isinstance(layer, L.DepthwiseConv2D):
+                stages.append(_Depthwise(self, layer, tin[0], tout))
                 continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
@@ -437,26 +452,34 @@ class LayerwisePlan(PG.ReplicaPlan):
 
 # ---------------------------------------------------------------------------------------
 class _Gemm(_Stage):
-    def __init__(self, plan, layer, tin, tout, stats):
+    def __init__(self, plan, layer, tin, tout, stats, pointwise=False):
+        """``pointwise``: the 1x1 / stride-1 / unpadded step of a SeparableConv2D on its ``pointwise_kernel``
+        (float32 plans: the depthwise stage in front of it exists there only)."""
         self.layer, self.inp, self.out = layer, tin, tout
         self.node_index = tout.producer
         self.stats = stats
         self.relu = layer.activation == "relu"
         st = plan.store
-        self.wname = f"{layer.name}/kernel"
+        self.wname = f"{layer.name}/{'pointwise_kernel' if pointwise else 'kernel'}"
         self.bname = f"{layer.name}/bias" if layer.use_bias else None
         self.W = st.view(self.wname)
         self.gW = st.grad(self.wname)
         self.b = st.view(self.bname) if self.bname else None
         self.gb = st.grad(self.bname) if self.bname else None
-        self.conv = isinstance(layer, L.Conv2D)
+        self.conv = pointwise or isinstance(layer, L.Conv2D)
         need_dgrad = tin.root().id != 0
         self.need_dgrad = need_dgrad
         self.f32 = plan.f32
         self.shadows = {} if self.f32 else {self.wname: ("row", "col") if need_dgrad else ("col",)}
         self.small_fwd = self.small_dgrad = self.small_wgrad = False
         self.use_im2col = self.use_stem_pack = False
-        if self.conv and self.f32:   # the f32 implicit GEMM covers every geometry itself
+        if self.conv:   # the convolution this stage computes (emulate_step reads these too)
+            self.kstrides = (1, 1) if pointwise else layer.strides
+            self.kpads = ((0, 0), (0, 0)) if pointwise else layer.pads(tin.shape)
+        if pointwise:
+            H, W_, C = tin.shape
+            self.geo = O.ConvGeom(plan.B, H, W_, C, H, W_, tout.C, 1, 1, 1, 1, 0, 0)
+        elif self.conv and self.f32:   # the f32 implicit GEMM covers every geometry itself
             H, W_, C = tin.shape
             Ho, Wo, Co = tout.shape
             (pt, _), (pl, _) = layer.pads(tin.shape)
@@ -860,6 +883,62 @@ class _MaxPool(_Stage):
                       accum=self.accum[self.inp.root().id])
 
 
+class _Depthwise(_Stage):
+    """DepthwiseConv2D, and the depthwise step of a SeparableConv2D (``head=False``: no bias, no activation),
+    on csrc/kernels/depthwise.hip — float32 forms only.  The ReLU backward is the (y > 0) mask the input- and
+    weight-gradient kernels apply while they stage dy: no act_bwd pass.  A following BatchNormalization
+    computes its own statistics (no statistics epilogue here)."""
+
+    def __init__(self, plan, layer, tin, tout, head=True):
+        who = f"{layer.name} ({type(layer).__name__})"
+        if not plan.f32:
+            raise Unsupported(f"{who}: the depthwise kernels are float32 only; the mixed_bfloat16 policy has none")
+        act = layer.activation if head else None
+        if act not in (None, "relu"):
+            raise Unsupported(f"{layer.name}: activation {act!r}")
+        self.layer, self.inp, self.out = layer, tin, tout
+        self.node_index = tout.producer
+        self.relu = act == "relu"
+        st = plan.store
+        self.wname = f"{layer.name}/depthwise_kernel"
+        self.bname = f"{layer.name}/bias" if head and layer.use_bias else None
+        self.W, self.gW = st.view(self.wname), st.grad(self.wname)
+        self.b = st.view(self.bname) if self.bname else None
+        self.gb = st.grad(self.bname) if self.bname else None
+        H, W_, C = tin.shape
+        Ho, Wo, Co = tout.shape
+        (pt, _), (pl, _) = layer.pads(tin.shape)
+        self.geo = O.ConvGeom(plan.B, H, W_, C, Ho, Wo, Co, layer.kernel_size[0], layer.kernel_size[1],
+                              layer.strides[0], layer.strides[1], pt, pl)
+        try:
+            O32.dw_check(self.geo, who)
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        self.need_dgrad = tin.root().id != 0
+
+    def alloc(self, B, dev):
+        pass
+
+    def wpart_need(self, B):
+        # ragged last batches run smaller geometries, and the split count is not monotone in the batch
+        return max(O32.dw_part_elems(self.geo.with_batch(b)) for b in range(1, B + 1))
+
+    def grad_inputs(self):
+        return [self.inp] if self.need_dgrad else []
+
+    def fwd(self, p, B, training, mode="train"):
+        O32.dw_fwd(self.inp.root().buf, self.W, self.out.root().buf, self.geo.with_batch(B), bias=self.b,
+                   relu=self.relu)
+
+    def bwd(self, p, B):
+        g = self.geo.with_batch(B)
+        dout = self.out.root().grad
+        y = self.out.root().buf if self.relu else None
+        O32.dw_wgrad(self.inp.root().buf, dout, self.gW, g, p.wpart, y=y, db=self.gb)
+        if self.need_dgrad:
+            O32.dw_dgrad(dout, self.W, self.inp.root().grad, g, y=y, accum=self.accum[self.inp.root().id])
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
@@ -1114,11 +1193,10 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
         if isinstance(stg, _Gemm):
             a = get(stg.inp)
             if stg.conv:
-                lay = stg.layer
-                (pt, pb), (pl, pr) = lay.pads(stg.inp.shape)
+                (pt, pb), (pl, pr) = stg.kpads
                 xc = F.pad(a.permute(0, 3, 1, 2), (pl, pr, pt, pb))
                 k = qw(stg.wname).permute(3, 2, 0, 1)
-                o = F.conv2d(xc, k, stride=lay.strides).permute(0, 2, 3, 1)
+                o = F.conv2d(xc, k, stride=stg.kstrides).permute(0, 2, 3, 1)
             else:
                 o = a.reshape(-1, a.shape[-1]) @ qw(stg.wname)
             if stg.bname:
@@ -1126,6 +1204,14 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             if stg.relu:
                 o = F.relu(o)
             vals[stg.out.root().id] = QR(o.reshape(B, -1))
+        elif isinstance(stg, _Depthwise):
+            lay = stg.layer
+            o = L._depthwise_ref(get(stg.inp), W[stg.wname], lay.strides, lay.pads(stg.inp.shape))   # groups = C
+            if stg.bname:
+                o = o + W[stg.bname]
+            if stg.relu:
+                o = F.relu(o)
+            vals[stg.out.root().id] = o.reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:

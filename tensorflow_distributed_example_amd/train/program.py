@@ -1166,10 +1166,10 @@ def make_plan(model, store, device, batch, global_batch, optimizer, loss, prefer
             if plan is not None:
                 return plan
         from . import layerwise
-        plan = layerwise.try_make(model, store, device, batch, global_batch, optimizer, loss)
-        if plan is not None:
-            return plan
-        raise NotImplementedError(
-            f"model {model.name!r} has layers without a HIP kernel path; set TDE_EXECUTOR=reference to run it "
-            "with torch reference ops")
+        try:
+            return layerwise.LayerwisePlan(model, store, device, batch, global_batch, optimizer, loss)
+        except layerwise.Unsupported as why:   # the last plan in line: its reason (layer, policy) goes to the user
+            raise NotImplementedError(
+                f"model {model.name!r} has layers without a HIP kernel path; set TDE_EXECUTOR=reference to run it "
+                f"with torch reference ops ({why})") from why
     return ReferencePlan(model, store, device, batch, global_batch, optimizer, loss)
