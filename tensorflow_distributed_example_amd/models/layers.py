@@ -626,6 +626,103 @@ class BatchNormalization(Layer):
                     scale=self.scale, **_reg_config(self, "beta_regularizer", "gamma_regularizer"))
 
 
+class _GroupNormBase(Layer):
+    """Batch-independent normalisation over groups of the last axis: y = (x - mean) * rsqrt(var + epsilon) * gamma
+    + beta with the population statistics of each (sample, group).  No moving state; training and inference
+    agree.  On the GPU: csrc/kernels/groupnorm.hip (float32 policy)."""
+
+    def _init_norm(self, axis, epsilon, center, scale, beta_initializer, gamma_initializer, beta_regularizer,
+                   gamma_regularizer):
+        self.axis = axis
+        self.epsilon = float(epsilon)
+        self.center = center
+        self.scale = scale
+        self.inits = (beta_initializer, gamma_initializer)
+        self.beta_regularizer = regularizers.get(beta_regularizer)
+        self.gamma_regularizer = regularizers.get(gamma_regularizer)
+
+    def _check_axis(self, input_shape):
+        if self.axis not in (-1, len(input_shape)):
+            raise ValueError(f"{type(self).__name__}: only the last axis (channels_last) is supported, got "
+                             f"axis={self.axis!r}")
+
+    def _add_affine(self, c):
+        if self.scale:
+            self.add_weight("gamma", (c,), self.inits[1], regularizer=self.gamma_regularizer)
+        if self.center:
+            self.add_weight("beta", (c,), self.inits[0], regularizer=self.beta_regularizer)
+
+    def _norm_config(self):
+        return dict(name=self.name, axis=self.axis, epsilon=self.epsilon, center=self.center, scale=self.scale,
+                    **_reg_config(self, "beta_regularizer", "gamma_regularizer"))
+
+
+class GroupNormalization(_GroupNormBase):
+    """Keras ``GroupNormalization`` on [N, H, W, C] and [N, C] inputs: statistics over positions x the C / groups
+    channels of a group; ``groups=1`` is whole-sample layer norm, ``groups=-1`` instance norm (groups = C)."""
+    _prefix = "group_normalization"
+
+    def __init__(self, groups=32, axis=-1, epsilon=1e-3, center=True, scale=True, beta_initializer="zeros",
+                 gamma_initializer="ones", beta_regularizer=None, gamma_regularizer=None, **kw):
+        super().__init__(**kw)
+        if isinstance(axis, (list, tuple)) or int(groups) == 0 or int(groups) < -1:
+            raise ValueError(f"GroupNormalization: groups={groups!r}, axis={axis!r}")
+        self.groups = int(groups)
+        self._init_norm(axis, epsilon, center, scale, beta_initializer, gamma_initializer, beta_regularizer,
+                        gamma_regularizer)
+
+    def build(self, input_shape):
+        self._check_axis(input_shape)
+        c = input_shape[-1]
+        if self.groups != -1 and c % self.groups:
+            raise ValueError(f"{self.name}: groups={self.groups} does not divide the {c} channels")
+        self._add_affine(c)
+        self.built = True
+
+    def n_groups(self, c):
+        return c if self.groups == -1 else self.groups
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        xc = x.movedim(-1, 1)
+        return F.group_norm(xc, self.n_groups(x.shape[-1]), W.get("gamma"), W.get("beta"),
+                            self.epsilon).movedim(1, -1)
+
+    def get_config(self):
+        return dict(groups=self.groups, **self._norm_config())
+
+
+class LayerNormalization(_GroupNormBase):
+    """Keras ``LayerNormalization`` over the last axis: every position of every sample is normalised over its C
+    channels (``gamma``, ``beta`` [C])."""
+    _prefix = "layer_normalization"
+
+    def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, beta_initializer="zeros",
+                 gamma_initializer="ones", beta_regularizer=None, gamma_regularizer=None, **kw):
+        super().__init__(**kw)
+        if isinstance(axis, (list, tuple)):
+            if len(axis) != 1:
+                raise ValueError(f"LayerNormalization: axis={list(axis)!r}: only the last axis is supported (Keras "
+                                 "would give gamma the shape of all listed axes); to normalise a whole sample use "
+                                 "GroupNormalization(groups=1)")
+            axis = axis[0]
+        self._init_norm(axis, epsilon, center, scale, beta_initializer, gamma_initializer, beta_regularizer,
+                        gamma_regularizer)
+
+    def build(self, input_shape):
+        self._check_axis(input_shape)
+        self._add_affine(input_shape[-1])
+        self.built = True
+
+    def n_groups(self, c):
+        return 1
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        return F.layer_norm(x, x.shape[-1:], W.get("gamma"), W.get("beta"), self.epsilon)
+
+    def get_config(self):
+        return self._norm_config()
+
+
 class Add(Layer):
     """Element-wise sum of same-shaped inputs (ResNet shortcut join)."""
     _prefix = "add"
@@ -804,7 +901,8 @@ class RandomZoom(_RandomAffine):
 
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
-                                         Dropout, BatchNormalization, Add, RandomFlip, RandomTranslation,
+                                         Dropout, BatchNormalization, GroupNormalization,
+                                         LayerNormalization, Add, RandomFlip, RandomTranslation,
                                          RandomRotation, RandomZoom]}
 
 

@@ -115,6 +115,24 @@ def mnist_separable_cnn(name=None):
     ], name=name)
 
 
+def mnist_gn_cnn(name=None):
+    """A small MNIST net on batch-independent norms: two GroupNormalization(8) convolution blocks and a
+    LayerNormalization Dense block (runs on the float32 layer-wise plan; csrc/kernels/groupnorm.hip)."""
+    return Sequential([
+        L.Conv2D(32, 3, input_shape=(28, 28, 1)),
+        L.GroupNormalization(8),
+        L.ReLU(),
+        L.Conv2D(64, 3, strides=2),
+        L.GroupNormalization(8),
+        L.ReLU(),
+        L.Flatten(),
+        L.Dense(128),
+        L.LayerNormalization(),
+        L.ReLU(),
+        L.Dense(10),
+    ], name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

@@ -37,6 +37,11 @@ N.register_hip({
     "tde_dwconv32_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),        # dy, y, w, dx, accum, geo, stream
     "tde_dwconv32_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),  # x, dy, y, dW, db, part, geo, stream
     "tde_dwconv32_splits": (_i, [_vp]),
+    # csrc/kernels/groupnorm.hip
+    "tde_gn32_plan": (_i, [_i, _i, _i, _i, _vp]),                                       # R, S, C, G, out[7]
+    "tde_gn32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),      # x, gamma, beta, y, mean, rstd
+    # dy, x, gamma, mean, rstd, dx, accum, dgamma, dbeta, part, R, S, C, G, stream
+    "tde_gn32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 })
 
 _NODROP = DropSpec()
@@ -244,6 +249,66 @@ def dw_wgrad(x, dy, dW, g: ConvGeom, part, y=None, db=None):
         _f32(db, g.Co, "dw_wgrad db")
     N.check(N.hip().tde_dwconv32_wgrad(_P(x), _P(dy), _P(y), _P(dW), _P(db), _P(part), g.carray(), _s()),
             "tde_dwconv32_wgrad")
+
+
+# ---------------------------------------------------------------- GroupNormalization / LayerNormalization
+GN_MAX_C = 2048
+
+
+def gn_check(R, S, C, G, what):
+    """The supported range of csrc/kernels/groupnorm.hip: R rows of S positions x C channels in G groups (group
+    (r, g): for each s the C // G floats at ((r*S + s)*C + g*(C // G))).  Returns (elements, groups)."""
+    _req(min(R, S, C, G) >= 1, f"{what}: empty geometry R={R} S={S} C={C} G={G}")
+    _req(C <= GN_MAX_C, f"{what}: {C} channels (at most {GN_MAX_C})")
+    _req(C % G == 0, f"{what}: {G} groups do not divide {C} channels")
+    _req(R * G < 2 ** 31 and R * S < 2 ** 31, f"{what}: R={R} S={S} G={G} past the 32-bit row range")
+    return R * S * C, R * G
+
+
+def gn_plan(R, S, C, G):
+    """How the kernel library splits a geometry (its own rule: one source of truth): dict(slab, parts, strip,
+    group_block, blocks, staged_fwd, staged_bwd); ``parts`` partial rows [2][C] feed the ordered reduction."""
+    gn_check(R, S, C, G, "gn_plan")
+    out = (_i * 7)()
+    N.check(min(N.hip().tde_gn32_plan(R, S, C, G, out), 0), "tde_gn32_plan")
+    return dict(zip(("slab", "parts", "strip", "group_block", "blocks", "staged_fwd", "staged_bwd"), out))
+
+
+def gn_part_elems(R, S, C, G):
+    """f32 elements of the partial rows [parts][2][C] of ``gn_bwd``."""
+    return gn_plan(R, S, C, G)["parts"] * 2 * C
+
+
+def gn_fwd(x, y, mean, rstd, R, S, C, G, eps, gamma=None, beta=None):
+    """y = (x - mean) * rstd * gamma + beta per (row, group); mean, rstd f32 [R*G] are saved for ``gn_bwd``."""
+    n, ng = gn_check(R, S, C, G, "gn_fwd")
+    _f32(x, n, "gn_fwd x")
+    _f32(y, n, "gn_fwd y")
+    _f32(mean, ng, "gn_fwd mean")
+    _f32(rstd, ng, "gn_fwd rstd")
+    if gamma is not None:
+        _f32(gamma, C, "gn_fwd gamma")
+    if beta is not None:
+        _f32(beta, C, "gn_fwd beta")
+    N.check(N.hip().tde_gn32_fwd(_P(x), _P(gamma), _P(beta), _P(y), _P(mean), _P(rstd), R, S, C, G, float(eps), _s()),
+            "tde_gn32_fwd")
+
+
+def gn_bwd(dy, x, mean, rstd, R, S, C, G, part, gamma=None, dx=None, accum=False, dgamma=None, dbeta=None):
+    """dx (+)= rstd * (g - mean_grp(g) - xh * mean_grp(g * xh)) with xh = (x - mean) * rstd, g = dy * gamma (dx
+    None: skipped); dgamma = sum dy * xh, dbeta = sum dy from per-workgroup partials in ``part``
+    (``gn_part_elems``), summed in a fixed order: bitwise reproducible."""
+    n, ng = gn_check(R, S, C, G, "gn_bwd")
+    _f32(dy, n, "gn_bwd dy")
+    _f32(x, n, "gn_bwd x")
+    _f32(mean, ng, "gn_bwd mean")
+    _f32(rstd, ng, "gn_bwd rstd")
+    _f32(part, gn_part_elems(R, S, C, G), "gn_bwd partials")
+    for t, m, what in ((gamma, C, "gamma"), (dx, n, "dx"), (dgamma, C, "dgamma"), (dbeta, C, "dbeta")):
+        if t is not None:
+            _f32(t, m, f"gn_bwd {what}")
+    N.check(N.hip().tde_gn32_bwd(_P(dy), _P(x), _P(gamma), _P(mean), _P(rstd), _P(dx), int(accum), _P(dgamma),
+                                 _P(dbeta), _P(part), R, S, C, G, _s()), "tde_gn32_bwd")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

@@ -233,6 +233,9 @@ class LayerwisePlan(PG.ReplicaPlan):
             if isinstance(layer, L.DepthwiseConv2D):
                 stages.append(_Depthwise(self, layer, tin[0], tout))
                 continue
+            if isinstance(layer, (L.GroupNormalization, L.LayerNormalization)):
+                stages.append(_GroupNorm(self, layer, tin[0], tout))   # no element-wise chain id: not a chain member
+                continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
@@ -939,6 +942,63 @@ class _Depthwise(_Stage):
             O32.dw_dgrad(dout, self.W, self.inp.root().grad, g, y=y, accum=self.accum[self.inp.root().id])
 
 
+class _GroupNorm(_Stage):
+    """GroupNormalization / LayerNormalization on csrc/kernels/groupnorm.hip — float32 forms only.  Geometry
+    (R rows, S positions, C channels, G groups): GroupNormalization (B, H*W or 1, C, groups), LayerNormalization
+    (B*H*W, 1, C, 1).  The stage owns the saved mean / rstd; a following ReLU is an _Elementwise stage."""
+
+    def __init__(self, plan, layer, tin, tout):
+        who = f"{layer.name} ({type(layer).__name__})"
+        if not plan.f32:
+            raise Unsupported(f"{who}: the group-norm kernels are float32 only; the mixed_bfloat16 policy has none")
+        self.layer, self.inp, self.out = layer, tin, tout
+        self.node_index = tout.producer
+        self.C = tin.C
+        self.G = layer.n_groups(self.C)
+        self.rowwise = isinstance(layer, L.LayerNormalization)
+        self.pos = tin.numel // self.C          # positions per sample
+        try:
+            O32.gn_check(*self.geom(plan.B), who)
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        st = plan.store
+        n = layer.name
+        self.gamma = st.view(f"{n}/gamma") if layer.scale else None
+        self.beta = st.view(f"{n}/beta") if layer.center else None
+        self.ggamma = st.grad(f"{n}/gamma") if layer.scale and st.segments[f"{n}/gamma"].trainable else None
+        self.gbeta = st.grad(f"{n}/beta") if layer.center and st.segments[f"{n}/beta"].trainable else None
+        self._pnames = [f"{n}/{v}" for v, g in (("gamma", self.ggamma), ("beta", self.gbeta)) if g is not None]
+        self.need_dgrad = tin.root().id != 0
+
+    def geom(self, B):
+        return (B * self.pos, 1, self.C, 1) if self.rowwise else (B, self.pos, self.C, self.G)
+
+    def param_names(self):
+        return self._pnames
+
+    def alloc(self, B, dev):
+        R, _, _, G = self.geom(B)
+        self.mean = torch.zeros(R * G, dtype=torch.float32, device=dev)
+        self.rstd = torch.zeros(R * G, dtype=torch.float32, device=dev)
+
+    def wpart_need(self, B):
+        # ragged last batches run smaller geometries: sized for every batch from 1 to B
+        return max(O32.gn_part_elems(*self.geom(b)) for b in range(1, B + 1))
+
+    def grad_inputs(self):
+        return [self.inp] if self.need_dgrad else []
+
+    def fwd(self, p, B, training, mode="train"):
+        O32.gn_fwd(self.inp.root().buf, self.out.root().buf, self.mean, self.rstd, *self.geom(B),
+                   self.layer.epsilon, gamma=self.gamma, beta=self.beta)
+
+    def bwd(self, p, B):
+        ir = self.inp.root()
+        O32.gn_bwd(self.out.root().grad, ir.buf, self.mean, self.rstd, *self.geom(B), p.wpart, gamma=self.gamma,
+                   dx=ir.grad if self.need_dgrad else None, accum=self.accum.get(ir.id, False),
+                   dgamma=self.ggamma, dbeta=self.gbeta)
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
@@ -1212,6 +1272,10 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             if stg.relu:
                 o = F.relu(o)
             vals[stg.out.root().id] = o.reshape(B, -1)
+        elif isinstance(stg, _GroupNorm):
+            lay = stg.layer
+            vals[stg.out.root().id] = lay.ref_call(get(stg.inp), {k: W[f"{lay.name}/{k}"] for k in ("gamma", "beta")
+                                                                  if f"{lay.name}/{k}" in W}, True).reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:
