@@ -723,6 +723,82 @@ class LayerNormalization(_GroupNormBase):
         return self._norm_config()
 
 
+class MultiHeadAttention(Layer):
+    """Keras ``MultiHeadAttention`` as self-attention: ``mha(x, x)`` or ``mha(x)`` on [N, T, D] or [N, H, W, D]
+    (the T = H*W positions in row-major order are the tokens); the output has the input's shape.
+        Q = x Wq + bq, K = x Wk + bk, V = x Wv + bv;  per head: O = softmax(Q K^T / sqrt(key_dim)) V;
+        y = concat_heads(O) Wo + bo
+    Weights in Keras's layout: ``query/kernel``, ``key/kernel`` [D, heads, key_dim], ``value/kernel``
+    [D, heads, value_dim], their biases [heads, dim], ``attention_output/kernel`` [heads, value_dim, D] and
+    ``attention_output/bias`` [D].  Cross-attention, masks, attention dropout and returned scores are refused.
+    On the GPU: csrc/kernels/attention.hip between 1x1 GEMM stages (float32 policy)."""
+    _prefix = "multi_head_attention"
+
+    def __init__(self, num_heads, key_dim, value_dim=None, dropout=0.0, use_bias=True, output_shape=None,
+                 attention_axes=None, kernel_initializer="glorot_uniform", bias_initializer="zeros",
+                 kernel_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(**kw)
+        for arg, val, ok in (("dropout", dropout, dropout == 0), ("attention_axes", attention_axes,
+                                                                  attention_axes is None),
+                             ("output_shape", output_shape, output_shape is None)):
+            if not ok:
+                raise NotImplementedError(f"MultiHeadAttention: {arg}={val!r} is not supported")
+        self.num_heads, self.key_dim = int(num_heads), int(key_dim)
+        self.value_dim = int(value_dim) if value_dim is not None else self.key_dim
+        if min(self.num_heads, self.key_dim, self.value_dim) < 1:
+            raise ValueError(f"MultiHeadAttention: num_heads={num_heads!r}, key_dim={key_dim!r}, "
+                             f"value_dim={value_dim!r}")
+        self.use_bias = use_bias
+        self.kernel_initializer, self.bias_initializer = kernel_initializer, bias_initializer
+        self.kernel_regularizer = regularizers.get(kernel_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
+
+    def __call__(self, query, value=None, key=None, attention_mask=None, return_attention_scores=False,
+                 training=None, use_causal_mask=False):
+        for arg, bad in (("value", value is not None and value is not query), ("key", key is not None and
+                                                                                 key is not query),
+                         ("attention_mask", attention_mask is not None),
+                         ("use_causal_mask", bool(use_causal_mask)),
+                         ("return_attention_scores", bool(return_attention_scores))):
+            if bad:
+                raise NotImplementedError(f"{self.name} (MultiHeadAttention): {arg}= is not supported: "
+                                          "self-attention only (mha(x, x)), no masks, no returned scores")
+        return super().__call__(query)
+
+    def projections(self):
+        """(variable prefix, per-head size) of the three input projections, in Keras's weight order."""
+        return (("query", self.key_dim), ("key", self.key_dim), ("value", self.value_dim))
+
+    def build(self, input_shape):
+        if len(input_shape) not in (2, 3):
+            raise ValueError(f"{self.name}: input [N, T, D] or [N, H, W, D] expected, got {(None,) + tuple(input_shape)}")
+        D, h = input_shape[-1], self.num_heads
+        specs = [(n, (D, h, d), (h, d)) for n, d in self.projections()]
+        for n, ks, bs in specs + [("attention_output", (h, self.value_dim, D), (D,))]:
+            self.add_weight(f"{n}/kernel", ks, self.kernel_initializer, regularizer=self.kernel_regularizer)
+            if self.use_bias:
+                self.add_weight(f"{n}/bias", bs, self.bias_initializer, regularizer=self.bias_regularizer)
+        self.built = True
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        N, D, h = x.shape[0], x.shape[-1], self.num_heads
+        xt = x.reshape(N, -1, D)
+
+        def dense(t, n):
+            k = W[f"{n}/kernel"]
+            y = t @ (k.reshape(D, -1) if n != "attention_output" else k.reshape(-1, D))
+            return y + W[f"{n}/bias"].reshape(-1) if self.use_bias else y
+
+        q, k, v = (dense(xt, n).reshape(N, -1, h, d).transpose(1, 2) for n, d in self.projections())
+        p = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(self.key_dim), dim=-1)
+        o = (p @ v).transpose(1, 2).reshape(N, -1, h * self.value_dim)
+        return dense(o, "attention_output").reshape(x.shape)
+
+    def get_config(self):
+        return dict(name=self.name, num_heads=self.num_heads, key_dim=self.key_dim, value_dim=self.value_dim,
+                    use_bias=self.use_bias, **_reg_config(self, "kernel_regularizer", "bias_regularizer"))
+
+
 class Add(Layer):
     """Element-wise sum of same-shaped inputs (ResNet shortcut join)."""
     _prefix = "add"
@@ -902,8 +978,8 @@ class RandomZoom(_RandomAffine):
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, GroupNormalization,
-                                         LayerNormalization, Add, RandomFlip, RandomTranslation,
-                                         RandomRotation, RandomZoom]}
+                                         LayerNormalization, MultiHeadAttention, Add, RandomFlip,
+                                         RandomTranslation, RandomRotation, RandomZoom]}
 
 
 def from_config(cls_name, cfg):

@@ -133,6 +133,24 @@ def mnist_gn_cnn(name=None):
     ], name=name)
 
 
+def mnist_attn_cnn(name=None):
+    """A conv-attention hybrid on MNIST: a 4x4 / stride-4 patch convolution to 7x7x32 (49 tokens), then one
+    pre-norm transformer block, self-attention (4 heads of 8) and a 1x1-convolution MLP, each under a residual
+    Add (functional API; runs on the float32 layer-wise plan; csrc/kernels/attention.hip)."""
+    from .model import Model
+    inp = L.Input((28, 28, 1))
+    x = L.Conv2D(32, 4, strides=4, activation="relu")(inp)
+    y = L.LayerNormalization()(x)
+    y = L.MultiHeadAttention(4, 8)(y, y)
+    x = L.Add()([y, x])
+    y = L.LayerNormalization()(x)
+    y = L.Conv2D(64, 1, activation="relu")(y)
+    y = L.Conv2D(32, 1)(y)
+    x = L.Add()([y, x])
+    x = L.GlobalAveragePooling2D()(x)
+    return Model(inputs=inp, outputs=L.Dense(10)(x), name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

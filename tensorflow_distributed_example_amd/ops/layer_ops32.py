@@ -42,6 +42,10 @@ N.register_hip({
     "tde_gn32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),      # x, gamma, beta, y, mean, rstd
     # dy, x, gamma, mean, rstd, dx, accum, dgamma, dbeta, part, R, S, C, G, stream
     "tde_gn32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # csrc/kernels/attention.hip
+    "tde_mha32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),         # q, k, v, o, lse, B, H, T, dk, dv
+    # q, k, v, o, lse, dO, dq, accum, dk, dv, B, H, T, dk, dv, stream
+    "tde_mha32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 })
 
 _NODROP = DropSpec()
@@ -309,6 +313,48 @@ def gn_bwd(dy, x, mean, rstd, R, S, C, G, part, gamma=None, dx=None, accum=False
             _f32(t, m, f"gn_bwd {what}")
     N.check(N.hip().tde_gn32_bwd(_P(dy), _P(x), _P(gamma), _P(mean), _P(rstd), _P(dx), int(accum), _P(dgamma),
                                  _P(dbeta), _P(part), R, S, C, G, _s()), "tde_gn32_bwd")
+
+
+# ---------------------------------------------------------------- MultiHeadAttention core (csrc/kernels/attention.hip)
+MHA_MAX_T, MHA_MAX_D = 256, 64
+
+
+def mha_check(B, H, T, dk, dv, what):
+    """The supported range of csrc/kernels/attention.hip: B samples, H heads, T tokens, head sizes dk (query /
+    key) and dv (value).  Returns the element counts of (Q or K, V or O, lse)."""
+    _req(min(B, H, T) >= 1, f"{what}: empty geometry B={B} heads={H} T={T}")
+    _req(T <= MHA_MAX_T, f"{what}: {T} tokens (at most {MHA_MAX_T})")
+    for d, n in ((dk, "key_dim"), (dv, "value_dim")):
+        _req(4 <= d <= MHA_MAX_D and d % 4 == 0, f"{what}: {n}={d} (a multiple of 4, at most {MHA_MAX_D})")
+    _req(B * H * -(-T // 64) < 2 ** 31, f"{what}: B={B} heads={H} past the 32-bit workgroup range")
+    return B * T * H * dk, B * T * H * dv, B * H * T
+
+
+def _mha_f32(t, n, what):
+    _f32(t, n, what)
+    _req(t.data_ptr() % 16 == 0, f"{what}: a 16-byte aligned base expected")
+
+
+def mha_fwd(q, k, v, o, lse, B, H, T, dk, dv):
+    """o [B,T,H*dv] = softmax(q k^T / sqrt(dk)) v per (sample, head), q / k [B,T,H*dk] and v [B,T,H*dv] head-major
+    in the last axis; lse f32 [B,H,T] (the row log-sum-exp of the scaled scores) is saved for ``mha_bwd``."""
+    nk, nv, nl = mha_check(B, H, T, dk, dv, "mha_fwd")
+    for t, n, what in ((q, nk, "q"), (k, nk, "k"), (v, nv, "v"), (o, nv, "o")):
+        _mha_f32(t, n, f"mha_fwd {what}")
+    _f32(lse, nl, "mha_fwd lse")
+    N.check(N.hip().tde_mha32_fwd(_P(q), _P(k), _P(v), _P(o), _P(lse), B, H, T, dk, dv, _s()), "tde_mha32_fwd")
+
+
+def mha_bwd(q, k, v, o, lse, do, dq, dk_, dv_, B, H, T, dk, dv, accum=False):
+    """dq (+)= , dk_ = , dv_ = the gradients of ``mha_fwd`` under ``do``; ``accum`` adds onto dq.  Two launches
+    (dK / dV per key block, dQ per query block), no atomics: bitwise reproducible."""
+    nk, nv, nl = mha_check(B, H, T, dk, dv, "mha_bwd")
+    for t, n, what in ((q, nk, "q"), (k, nk, "k"), (v, nv, "v"), (o, nv, "o"), (do, nv, "do"), (dq, nk, "dq"),
+                       (dk_, nk, "dk"), (dv_, nv, "dv")):
+        _mha_f32(t, n, f"mha_bwd {what}")
+    _f32(lse, nl, "mha_bwd lse")
+    N.check(N.hip().tde_mha32_bwd(_P(q), _P(k), _P(v), _P(o), _P(lse), _P(do), _P(dq), int(accum), _P(dk_), _P(dv_),
+                                  B, H, T, dk, dv, _s()), "tde_mha32_bwd")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

@@ -236,6 +236,30 @@ class LayerwisePlan(PG.ReplicaPlan):
             if isinstance(layer, (L.GroupNormalization, L.LayerNormalization)):
                 stages.append(_GroupNorm(self, layer, tin[0], tout))   # no element-wise chain id: not a chain member
                 continue
+            if isinstance(layer, L.MultiHeadAttention):
+                # three 1x1 GEMM stages (Q, K, V: all read x, so their input gradients meet in x.grad by the
+                # multi-consumer rule), the attention core over internal tensors, the output projection
+                who = f"{layer.name} (MultiHeadAttention)"
+                if not self.f32:
+                    raise Unsupported(f"{who}: the attention kernels are float32 only; the mixed_bfloat16 policy "
+                                      "has none")
+                grid = tin[0].shape[:-1]
+
+                def mid(width):
+                    t = _T(max(T) + 1, grid + (width,))
+                    t.producer, t.consumers = i, [i]
+                    T[t.id] = t
+                    return t
+
+                qkv = [mid(layer.num_heads * d) for _, d in layer.projections()]
+                for (n, _), t in zip(layer.projections(), qkv):
+                    stages.append(_Gemm(self, layer, tin[0], t, False, pointwise=True,
+                                        names=(f"{n}/kernel", f"{n}/bias")))
+                o = mid(layer.num_heads * layer.value_dim)
+                stages.append(_Attention(self, layer, qkv, o))
+                stages.append(_Gemm(self, layer, o, tout, False, pointwise=True,
+                                    names=("attention_output/kernel", "attention_output/bias")))
+                continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
@@ -455,16 +479,19 @@ class LayerwisePlan(PG.ReplicaPlan):
 
 # ---------------------------------------------------------------------------------------
 class _Gemm(_Stage):
-    def __init__(self, plan, layer, tin, tout, stats, pointwise=False):
-        """``pointwise``: the 1x1 / stride-1 / unpadded step of a SeparableConv2D on its ``pointwise_kernel``
-        (float32 plans: the depthwise stage in front of it exists there only)."""
+    def __init__(self, plan, layer, tin, tout, stats, pointwise=False, names=None):
+        """``pointwise``: a 1x1 / stride-1 / unpadded step of a composite layer on the token grid of ``tin``
+        (float32 plans: the stages around it exist there only).  ``names``: the layer's (kernel, bias) variables
+        the step runs on, any shape that flattens to [C, Co] and [Co] — default: a SeparableConv2D's
+        ``pointwise_kernel`` and ``bias``, with the layer's activation; a named step has none."""
         self.layer, self.inp, self.out = layer, tin, tout
         self.node_index = tout.producer
         self.stats = stats
-        self.relu = layer.activation == "relu"
+        self.relu = names is None and layer.activation == "relu"
         st = plan.store
-        self.wname = f"{layer.name}/{'pointwise_kernel' if pointwise else 'kernel'}"
-        self.bname = f"{layer.name}/bias" if layer.use_bias else None
+        kname, bname = names or ("pointwise_kernel" if pointwise else "kernel", "bias")
+        self.wname = f"{layer.name}/{kname}"
+        self.bname = f"{layer.name}/{bname}" if layer.use_bias else None
         self.W = st.view(self.wname)
         self.gW = st.grad(self.wname)
         self.b = st.view(self.bname) if self.bname else None
@@ -480,7 +507,8 @@ class _Gemm(_Stage):
             self.kstrides = (1, 1) if pointwise else layer.strides
             self.kpads = ((0, 0), (0, 0)) if pointwise else layer.pads(tin.shape)
         if pointwise:
-            H, W_, C = tin.shape
+            C = tin.C
+            H, W_ = tin.shape[0], tin.numel // (tin.shape[0] * C)   # [T, D] tokens: a T x 1 grid
             self.geo = O.ConvGeom(plan.B, H, W_, C, H, W_, tout.C, 1, 1, 1, 1, 0, 0)
         elif self.conv and self.f32:   # the f32 implicit GEMM covers every geometry itself
             H, W_, C = tin.shape
@@ -999,6 +1027,47 @@ class _GroupNorm(_Stage):
                    dgamma=self.ggamma, dbeta=self.gbeta)
 
 
+class _Attention(_Stage):
+    """The core of a MultiHeadAttention on csrc/kernels/attention.hip — float32 forms only: O = softmax(Q K^T /
+    sqrt(dk)) V per (sample, head) over the internal Q, K, V tensors [T, heads * d] that the projection stages
+    wrote.  The stage owns lse [B, heads, T], all that the forward saves; the backward needs no partial buffer
+    (its dQ sweep has one writer per element).  Geometry: (B, heads, T, dk, dv)."""
+
+    def __init__(self, plan, layer, qkv, tout):
+        who = f"{layer.name} (MultiHeadAttention)"
+        self.layer, self.qkv, self.out = layer, qkv, tout
+        self.inp = qkv[0]
+        self.node_index = tout.producer
+        self.T = tout.numel // tout.C
+        try:
+            O32.mha_check(*self.geom(plan.B), who)
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+
+    def geom(self, B):
+        lay = self.layer
+        return (B, lay.num_heads, self.T, lay.key_dim, lay.value_dim)
+
+    def param_names(self):
+        return []
+
+    def alloc(self, B, dev):
+        self.lse = torch.zeros(B * self.layer.num_heads * self.T, dtype=torch.float32, device=dev)
+
+    def grad_inputs(self):
+        return list(self.qkv)
+
+    def fwd(self, p, B, training, mode="train"):
+        q, k, v = (t.root().buf for t in self.qkv)
+        O32.mha_fwd(q, k, v, self.out.root().buf, self.lse, *self.geom(B))
+
+    def bwd(self, p, B):
+        q, k, v = (t.root() for t in self.qkv)
+        o = self.out.root()
+        O32.mha_bwd(q.buf, k.buf, v.buf, o.buf, self.lse, o.grad, q.grad, k.grad, v.grad, *self.geom(B),
+                    accum=self.accum[q.id])
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
@@ -1253,14 +1322,15 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
         if isinstance(stg, _Gemm):
             a = get(stg.inp)
             if stg.conv:
+                g = stg.geo   # a pointwise step's variables flatten to [1, 1, C, Co] and [Co]
                 (pt, pb), (pl, pr) = stg.kpads
-                xc = F.pad(a.permute(0, 3, 1, 2), (pl, pr, pt, pb))
-                k = qw(stg.wname).permute(3, 2, 0, 1)
+                xc = F.pad(a.reshape(B, g.H, g.W, g.C).permute(0, 3, 1, 2), (pl, pr, pt, pb))
+                k = qw(stg.wname).reshape(g.KH, g.KW, g.C, g.Co).permute(3, 2, 0, 1)
                 o = F.conv2d(xc, k, stride=stg.kstrides).permute(0, 2, 3, 1)
             else:
                 o = a.reshape(-1, a.shape[-1]) @ qw(stg.wname)
             if stg.bname:
-                o = o + W[stg.bname]
+                o = o + W[stg.bname].reshape(-1)
             if stg.relu:
                 o = F.relu(o)
             vals[stg.out.root().id] = QR(o.reshape(B, -1))
@@ -1276,6 +1346,11 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             lay = stg.layer
             vals[stg.out.root().id] = lay.ref_call(get(stg.inp), {k: W[f"{lay.name}/{k}"] for k in ("gamma", "beta")
                                                                   if f"{lay.name}/{k}" in W}, True).reshape(B, -1)
+        elif isinstance(stg, _Attention):
+            _, h, T_, dk, dv = stg.geom(B)
+            q, k, v = (get(t).reshape(B, T_, h, -1).transpose(1, 2) for t in stg.qkv)
+            pr = torch.softmax(q @ k.transpose(-1, -2) / dk ** 0.5, dim=-1)
+            vals[stg.out.root().id] = (pr @ v).transpose(1, 2).reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:
