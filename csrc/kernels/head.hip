@@ -46,6 +46,8 @@ struct HeadArgs {
 
 constexpr int HR = 16;          // rows per workgroup
 constexpr int HMAX = 256;       // max hidden width
+constexpr int HCMAX = 16;       // max classes (one MFMA tile of logits)
+constexpr int HMULT = 4;        // H and ldh are multiples of it (float4 / bf16x4 loads of h)
 constexpr int HST = HMAX + 4;   // LDS row stride of h (floats; +4 breaks bank aliasing)
 
 __device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) {
@@ -248,6 +250,16 @@ __global__ __launch_bounds__(256) void head_xent_kernel(HeadArgs a) {
 
 using namespace tde;
 
+// {max classes, max hidden width, multiple of H and ldh, rows per workgroup}: the one statement of the head's
+// limits; ops/kernels.py (head_limits) and through it the layer-wise plan read them here.
+TDE_API int tde_head_limits(int* out) {
+  out[0] = HCMAX;
+  out[1] = HMAX;
+  out[2] = HMULT;
+  out[3] = HR;
+  return 0;
+}
+
 TDE_API int tde_head_xent(const float* hin, int ldh, const float* pre_bias, int pre_relu,
                           const float* W2, const float* b2, const int* labels, int B, int H,
                           int C, float scale, int compute_grad, float* dW2, float* db2,
@@ -255,7 +267,7 @@ TDE_API int tde_head_xent(const float* hin, int ldh, const float* pre_bias, int 
                           int ldgf, float* metrics, float* probs, int probs_are_logits,
                           float* row_loss, int zero_hin, long long* iterations, long long* stamps,
                           int hin_bf16, hipStream_t stream) {
-  if (C > 16 || H > HMAX || H % 4 || (ldh & 3)) return -1;
+  if (C > HCMAX || H > HMAX || H % HMULT || ldh % HMULT) return -1;
   if (hin_bf16 ? (((uintptr_t)hin & 7) || zero_hin) : (((uintptr_t)hin | (uintptr_t)pre_bias) & 15)) return -2;
   HeadArgs a{hin_bf16 ? nullptr : hin, ldh, hin_bf16 ? (const bf16*)hin : nullptr, pre_bias, pre_relu, W2, b2,
              labels, B, H, C, scale, compute_grad, dW2, db2, dpre_bias, (bf16*)G, ldg, (bf16*)Gt, ldgt, Gf, ldgf,

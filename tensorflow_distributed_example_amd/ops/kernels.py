@@ -209,15 +209,54 @@ def conv3x3c1_relu_pool_bwd(x, amax, G, W1, dw, db):
     N.check(rc, "tde_conv3x3c1_relu_pool_bwd")
 
 
+_HEAD_LIMITS = None
+
+
+def head_limits():
+    """The fused head's limits as csrc/kernels/head.hip states them (tde_head_limits): ``max_c`` classes,
+    ``max_h`` input features, ``h_mult`` (H and the row stride of hin are multiples of it), ``rows`` per
+    workgroup.  head_xent, head_fits and the layer-wise plan's fused-head rule all read them here."""
+    global _HEAD_LIMITS
+    if _HEAD_LIMITS is None:
+        out = (_ct.c_int * 4)()
+        N.check(N.hip().tde_head_limits(out), "tde_head_limits")
+        _HEAD_LIMITS = dict(max_c=out[0], max_h=out[1], h_mult=out[2], rows=out[3])
+    return _HEAD_LIMITS
+
+
+def head_fits(H, C):
+    """Does a Dense(C) on H input features fit the fused head kernel?"""
+    lim = head_limits()
+    return 1 <= C <= lim["max_c"] and 1 <= H <= lim["max_h"] and H % lim["h_mult"] == 0
+
+
+def head_check(hin, W2, labels, *, B, pre_bias=None, zero_hin=False):
+    """The preconditions of head_xent: everything tde_head_xent refuses (csrc/kernels/head.hip) is refused here
+    first, before any launch, by a ValueError that names the argument."""
+    H, C = W2.shape
+    hb = hin.dtype == torch.bfloat16
+    lim = head_limits()
+    _req((hin.dtype == torch.float32 or hb) and hin.dim() == 2 and hin.shape[0] >= B and hin.shape[1] >= H
+         and hin.stride(1) == 1, "head: hin must be an f32 or bf16 [B, H] input")
+    _req(1 <= C <= lim["max_c"], f"head: W2 has C = {C} classes, the fused head takes 1..{lim['max_c']}")
+    _req(1 <= H <= lim["max_h"] and H % lim["h_mult"] == 0,
+         f"head: W2 has H = {H} rows, the fused head takes multiples of {lim['h_mult']} up to {lim['max_h']}")
+    _req(hin.stride(0) % lim["h_mult"] == 0, f"head: hin row stride (ldh) must be a multiple of {lim['h_mult']}")
+    _req(not (hb and zero_hin), "head: zero_hin needs an f32 hin")
+    if hb:
+        _req(hin.data_ptr() % 8 == 0, "head: bf16 hin must be 8-byte aligned")
+    else:
+        _req(hin.data_ptr() % 16 == 0, "head: f32 hin must be 16-byte aligned")
+        _req(pre_bias is None or pre_bias.data_ptr() % 16 == 0, "head: pre_bias must be 16-byte aligned")
+    _req(labels.dtype == torch.int32, "head: int32 labels")
+
+
 def head_xent(hin, W2, b2, labels, *, B, scale, pre_bias=None, pre_relu=False, compute_grad=True,
               dW2=None, db2=None, dpre_bias=None, G=None, Gt=None, Gf=None, metrics=None,
               probs=None, probs_are_logits=False, row_loss=None, zero_hin=False, iterations=None, stamps=None):
+    head_check(hin, W2, labels, B=B, pre_bias=pre_bias, zero_hin=zero_hin)
     H, C = W2.shape
     hb = hin.dtype == torch.bfloat16
-    _req((hin.dtype == torch.float32 or hb and not zero_hin) and hin.dim() == 2 and hin.shape[1] >= H
-         and hin.stride(1) == 1, "head: f32 or bf16 [B, H] input")
-    _req(C <= 64 and H * C <= 16384, "head: too large for the fused head")
-    _req(labels.dtype == torch.int32, "head: int32 labels")
     ldg = G.stride(0) if G is not None else 0
     ldgt = Gt.stride(0) if Gt is not None else 0
     ldgf = Gf.stride(0) if Gf is not None else 0

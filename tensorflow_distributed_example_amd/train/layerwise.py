@@ -1148,9 +1148,9 @@ class _Head(_Stage):
         self.f32 = plan.f32
         # a non-trivial loss spec takes the general path, with the spec kernel in place of xent; metrics beyond
         # the accuracy take it too: their launch reads the logits buffer
-        self.fused = (not self.f32 and not plan.det and self.C <= 16 and self.H <= 256 and self.H % 4 == 0
-                      and not plan.loss_spec and not plan.metric_spec
-                      and os.environ.get("TDE_FUSED_HEAD", "1") != "0")
+        from ..ops.kernels import head_fits
+        self.fused = (not self.f32 and not plan.det and not plan.loss_spec and not plan.metric_spec
+                      and os.environ.get("TDE_FUSED_HEAD", "1") != "0" and head_fits(self.H, self.C))
         self.shadows = {} if (self.fused or self.f32) else {self.wname: ("row", "col") if self.need_dgrad else ("col",)}
         self.pre = None   # absorbed Dense: its ReLU mask and bias gradient are applied by the head launch
 
