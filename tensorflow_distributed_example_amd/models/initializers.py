@@ -67,9 +67,20 @@ def ones(shape, gen=None):
     return torch.ones(shape)
 
 
+def orthogonal(shape, gen):
+    """Keras ``Orthogonal`` (gain 1): Q of the QR factorisation of a normal [max, min] matrix, the signs of R's
+    diagonal folded in so the result is uniform over the orthogonal matrices; a flat [rows, cols] has
+    orthonormal rows or columns, whichever are fewer."""
+    rows, cols = int(np.prod(shape[:-1])), int(shape[-1])
+    a = torch.randn((max(rows, cols), min(rows, cols)), generator=gen, dtype=torch.float64)
+    q, r = torch.linalg.qr(a)
+    q = q * torch.sign(torch.diagonal(r))
+    return (q.T if rows < cols else q).reshape(shape).float()
+
+
 _REG = {
     "glorot_uniform": glorot_uniform, "glorot_normal": glorot_normal, "he_normal": he_normal,
-    "he_uniform": he_uniform, "zeros": zeros, "ones": ones,
+    "he_uniform": he_uniform, "zeros": zeros, "ones": ones, "orthogonal": orthogonal,
 }
 
 

@@ -799,6 +799,94 @@ class MultiHeadAttention(Layer):
                     use_bias=self.use_bias, **_reg_config(self, "kernel_regularizer", "bias_regularizer"))
 
 
+def _unit_forget_bias(units, rest):
+    """Keras's ``unit_forget_bias``: ones on the forget block [u:2u] of the [4u] bias, ``rest`` elsewhere."""
+    def init(shape, gen):
+        b = initializers.get(rest)(shape, gen).clone()
+        b[units:2 * units] = 1.0
+        return b
+    return init
+
+
+class LSTM(Layer):
+    """Keras ``LSTM`` on [N, T, D]: the last h [N, units], or every h [N, T, units] with ``return_sequences``.
+    From a zero state, with a_t = x_t W + b + h_{t-1} U in Keras's gate order i, f, c, o along the 4*units axis:
+        i, f, o = sigmoid(a_i), sigmoid(a_f), sigmoid(a_o);  g = tanh(a_c)
+        c_t = f * c_{t-1} + i * g;  h_t = o * tanh(c_t)
+    Weights under Keras's nested names: ``lstm_cell/kernel`` [D, 4u], ``lstm_cell/recurrent_kernel`` [u, 4u],
+    ``lstm_cell/bias`` [4u].  Other activations, dropout, masks, initial and returned state, ``go_backwards``,
+    ``stateful`` and ``unroll`` are refused.  On the GPU: a 1x1 GEMM stage for x W + b over all N*T tokens, then
+    the resident sweep of csrc/kernels/lstm.hip (float32 policy)."""
+    _prefix = "lstm"
+
+    def __init__(self, units, activation="tanh", recurrent_activation="sigmoid", use_bias=True,
+                 kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
+                 unit_forget_bias=True, kernel_regularizer=None, recurrent_regularizer=None, bias_regularizer=None,
+                 dropout=0.0, recurrent_dropout=0.0, return_sequences=False, return_state=False, go_backwards=False,
+                 stateful=False, unroll=False, **kw):
+        super().__init__(**kw)
+        for arg, val, ok in (("activation", activation, activation == "tanh"),
+                             ("recurrent_activation", recurrent_activation, recurrent_activation == "sigmoid"),
+                             ("dropout", dropout, dropout == 0), ("recurrent_dropout", recurrent_dropout,
+                                                                  recurrent_dropout == 0),
+                             ("return_state", return_state, not return_state),
+                             ("go_backwards", go_backwards, not go_backwards), ("stateful", stateful, not stateful),
+                             ("unroll", unroll, not unroll)):
+            if not ok:
+                raise NotImplementedError(f"LSTM: {arg}={val!r} is not supported")
+        self.units = int(units)
+        if self.units < 1:
+            raise ValueError(f"LSTM: units={units!r}")
+        self.use_bias, self.unit_forget_bias = use_bias, unit_forget_bias
+        self.return_sequences = bool(return_sequences)
+        self.kernel_initializer, self.recurrent_initializer = kernel_initializer, recurrent_initializer
+        self.bias_initializer = bias_initializer
+        self.kernel_regularizer = regularizers.get(kernel_regularizer)
+        self.recurrent_regularizer = regularizers.get(recurrent_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
+
+    def __call__(self, inputs, mask=None, training=None, initial_state=None):
+        for arg, val in (("mask", mask), ("initial_state", initial_state)):
+            if val is not None:
+                raise NotImplementedError(f"{self.name} (LSTM): {arg}= is not supported: whole sequences from a "
+                                          "zero state only")
+        return super().__call__(inputs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 2:
+            raise ValueError(f"{self.name}: input [N, T, D] expected, got {(None,) + tuple(input_shape)}")
+        u = self.units
+        self.add_weight("lstm_cell/kernel", (input_shape[-1], 4 * u), self.kernel_initializer,
+                        regularizer=self.kernel_regularizer)
+        self.add_weight("lstm_cell/recurrent_kernel", (u, 4 * u), self.recurrent_initializer,
+                        regularizer=self.recurrent_regularizer)
+        if self.use_bias:
+            init = _unit_forget_bias(u, self.bias_initializer) if self.unit_forget_bias else self.bias_initializer
+            self.add_weight("lstm_cell/bias", (4 * u,), init, regularizer=self.bias_regularizer)
+        self.built = True
+
+    def compute_output_shape(self, s):
+        return (s[0], self.units) if self.return_sequences else (self.units,)
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        z = x @ W["lstm_cell/kernel"]
+        if self.use_bias:
+            z = z + W["lstm_cell/bias"]
+        h = c = x.new_zeros(x.shape[0], self.units)
+        hs = []
+        for t in range(x.shape[1]):
+            i, f, g, o = (z[:, t] + h @ W["lstm_cell/recurrent_kernel"]).split(self.units, dim=-1)
+            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+            h = torch.sigmoid(o) * torch.tanh(c)
+            hs.append(h)
+        return torch.stack(hs, 1) if self.return_sequences else h
+
+    def get_config(self):
+        return dict(name=self.name, units=self.units, use_bias=self.use_bias,
+                    unit_forget_bias=self.unit_forget_bias, return_sequences=self.return_sequences,
+                    **_reg_config(self, "kernel_regularizer", "recurrent_regularizer", "bias_regularizer"))
+
+
 class Add(Layer):
     """Element-wise sum of same-shaped inputs (ResNet shortcut join)."""
     _prefix = "add"
@@ -978,7 +1066,7 @@ class RandomZoom(_RandomAffine):
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, GroupNormalization,
-                                         LayerNormalization, MultiHeadAttention, Add, RandomFlip,
+                                         LayerNormalization, MultiHeadAttention, LSTM, Add, RandomFlip,
                                          RandomTranslation, RandomRotation, RandomZoom]}
 
 

@@ -151,6 +151,18 @@ def mnist_attn_cnn(name=None):
     return Model(inputs=inp, outputs=L.Dense(10)(x), name=name)
 
 
+def mnist_lstm(name=None):
+    """MNIST read as 28 time steps of 28 features, the classic Keras RNN example: two stacked LSTM(64), the
+    first returning its sequence (so the second's input gradient runs back through a recurrence), then the
+    classifier (runs on the float32 layer-wise plan; csrc/kernels/lstm.hip)."""
+    return Sequential([
+        L.Reshape((28, 28), input_shape=(28, 28, 1)),
+        L.LSTM(64, return_sequences=True),
+        L.LSTM(64),
+        L.Dense(10),
+    ], name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

@@ -46,6 +46,9 @@ N.register_hip({
     "tde_mha32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),         # q, k, v, o, lse, B, H, T, dk, dv
     # q, k, v, o, lse, dO, dq, accum, dk, dv, B, H, T, dk, dv, stream
     "tde_mha32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # csrc/kernels/lstm.hip
+    "tde_lstm32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),   # z, U, hseq, hprev, gates, cseq, hlast, B, T, u
+    "tde_lstm32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),         # gates, cseq, U, dh, dz, B, T, u, last_only
 })
 
 _NODROP = DropSpec()
@@ -355,6 +358,46 @@ def mha_bwd(q, k, v, o, lse, do, dq, dk_, dv_, B, H, T, dk, dv, accum=False):
     _f32(lse, nl, "mha_bwd lse")
     N.check(N.hip().tde_mha32_bwd(_P(q), _P(k), _P(v), _P(o), _P(lse), _P(do), _P(dq), int(accum), _P(dk_), _P(dv_),
                                   B, H, T, dk, dv, _s()), "tde_mha32_bwd")
+
+
+# ---------------------------------------------------------------- LSTM recurrence (csrc/kernels/lstm.hip)
+LSTM_MIN_UNITS, LSTM_MAX_UNITS = 16, 128
+
+
+def lstm_check(B, T, units, what):
+    """The supported range of csrc/kernels/lstm.hip: B sequences of T steps, ``units`` hidden units.  Returns the
+    element count of a [B, T, units] tensor."""
+    _req(min(B, T) >= 1, f"{what}: empty geometry B={B} T={T}")
+    _req(LSTM_MIN_UNITS <= units <= LSTM_MAX_UNITS and units % 16 == 0,
+         f"{what}: units={units} (a multiple of 16 from {LSTM_MIN_UNITS} to {LSTM_MAX_UNITS})")
+    _req(T * units < 2 ** 24, f"{what}: T={T} x units={units} (a workgroup's 16 sequences are addressed by 32-bit "
+                              "byte offsets: T * units below 2^24)")
+    return B * T * units
+
+
+def lstm_fwd(z, rk, hseq, hprev, gates, cseq, B, T, units, hlast=None):
+    """The forward sweep over z = x W + b [B, T, 4 units] (gate order i, f, c, o) with the recurrent kernel rk
+    [units, 4 units] from a zero state: hseq (h_t), hprev (h_{t-1}, zeros at t = 0) and cseq [B, T, units], the
+    four gate activations ``gates`` [B, T, 4 units], and the last h into ``hlast`` [B, units] when given."""
+    n = lstm_check(B, T, units, "lstm_fwd")
+    for t, k, what in ((z, 4 * n, "z"), (rk, 4 * units * units, "recurrent kernel"), (hseq, n, "hseq"),
+                       (hprev, n, "hprev"), (gates, 4 * n, "gates"), (cseq, n, "cseq")):
+        _f32(t, k, f"lstm_fwd {what}")
+    if hlast is not None:
+        _f32(hlast, B * units, "lstm_fwd hlast")
+    N.check(N.hip().tde_lstm32_fwd(_P(z), _P(rk), _P(hseq), _P(hprev), _P(gates), _P(cseq), _P(hlast), B, T, units,
+                                   _s()), "tde_lstm32_fwd")
+
+
+def lstm_bwd(gates, cseq, rk, dh, dz, B, T, units, last_only):
+    """dz [B, T, 4 units] = the gradient of ``lstm_fwd``'s z under dh, the gradient of hseq [B, T, units] or, with
+    ``last_only``, of the last h alone [B, units].  One launch, no atomics: bitwise reproducible."""
+    n = lstm_check(B, T, units, "lstm_bwd")
+    for t, k, what in ((gates, 4 * n, "gates"), (cseq, n, "cseq"), (rk, 4 * units * units, "recurrent kernel"),
+                       (dh, B * units if last_only else n, "dh"), (dz, 4 * n, "dz")):
+        _f32(t, k, f"lstm_bwd {what}")
+    N.check(N.hip().tde_lstm32_bwd(_P(gates), _P(cseq), _P(rk), _P(dh), _P(dz), B, T, units, int(bool(last_only)),
+                                   _s()), "tde_lstm32_bwd")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

@@ -260,6 +260,19 @@ class LayerwisePlan(PG.ReplicaPlan):
                 stages.append(_Gemm(self, layer, o, tout, False, pointwise=True,
                                     names=("attention_output/kernel", "attention_output/bias")))
                 continue
+            if isinstance(layer, L.LSTM):
+                # the input projection x W + b over all B*T tokens as one 1x1 GEMM stage into an internal tensor,
+                # then the recurrence: one resident sweep per direction (csrc/kernels/lstm.hip)
+                if not self.f32:
+                    raise Unsupported(f"{layer.name} (LSTM): the recurrence kernels are float32 only; the "
+                                      "mixed_bfloat16 policy has none")
+                z = _T(max(T) + 1, (tin[0].shape[0], 4 * layer.units))
+                z.producer, z.consumers = i, [i]
+                T[z.id] = z
+                stages.append(_Gemm(self, layer, tin[0], z, False, pointwise=True,
+                                    names=("lstm_cell/kernel", "lstm_cell/bias")))
+                stages.append(_Lstm(self, layer, z, tout))
+                continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
@@ -1068,6 +1081,54 @@ class _Attention(_Stage):
                     accum=self.accum[q.id])
 
 
+class _Lstm(_Stage):
+    """The recurrence of an LSTM on csrc/kernels/lstm.hip — float32 forms only — over the internal tensor
+    z = x W + b [T, 4 units] that the projection stage wrote.  The stage owns what the forward saves: hprev
+    (h_{t-1} per token, the left operand of dU), the gate activations, cseq and, unless the layer returns its
+    sequence (then the output tensor is hseq), hseq.  The backward sweep writes z.grad, the projection stage's
+    output gradient; dU = hprev^T dZ over the B*T tokens is one weight-gradient GEMM.  Geometry: (B, T, units)."""
+
+    def __init__(self, plan, layer, z, tout):
+        self.layer, self.inp, self.out = layer, z, tout
+        self.node_index = tout.producer
+        self.T, self.units, self.seq = z.shape[0], layer.units, layer.return_sequences
+        try:
+            O32.lstm_check(*self.geom(plan.B), f"{layer.name} (LSTM)")
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        self.uname = f"{layer.name}/lstm_cell/recurrent_kernel"
+        self.U = plan.store.view(self.uname)
+        self.gU = plan.store.grad(self.uname)
+
+    def geom(self, B):
+        return (B, self.T, self.units)
+
+    def param_names(self):
+        return [self.uname]
+
+    def alloc(self, B, dev):
+        n = B * self.T * self.units
+        self.hprev, self.cseq = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(2))
+        self.gates = torch.zeros(4 * n, dtype=torch.float32, device=dev)
+        self.hseq = None if self.seq else torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def wpart_need(self, B):
+        return O32.wgrad_part_elems(self.units, 4 * self.units, B * self.T)
+
+    def grad_inputs(self):
+        return [self.inp]
+
+    def fwd(self, p, B, training, mode="train"):
+        out = self.out.root().buf
+        O32.lstm_fwd(self.inp.root().buf, self.U, out if self.seq else self.hseq, self.hprev, self.gates, self.cseq,
+                     *self.geom(B), hlast=None if self.seq else out)
+
+    def bwd(self, p, B):
+        dz = self.inp.root().grad   # z has this one consumer: written, never accumulated
+        O32.lstm_bwd(self.gates, self.cseq, self.U, self.out.root().grad, dz, *self.geom(B), last_only=not self.seq)
+        O32.dense_wgrad(self.hprev, dz, self.gU.view(self.units, -1), B * self.T, part=p.wpart)
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
@@ -1351,6 +1412,17 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             q, k, v = (get(t).reshape(B, T_, h, -1).transpose(1, 2) for t in stg.qkv)
             pr = torch.softmax(q @ k.transpose(-1, -2) / dk ** 0.5, dim=-1)
             vals[stg.out.root().id] = (pr @ v).transpose(1, 2).reshape(B, -1)
+        elif isinstance(stg, _Lstm):
+            _, T_, u = stg.geom(B)
+            zz, Uk = get(stg.inp), W[stg.uname]
+            h = c = zz.new_zeros(B, u)
+            hs = []
+            for t in range(T_):
+                gi, gf, gg, go = (zz[:, t] + h @ Uk).split(u, dim=-1)
+                c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+                h = torch.sigmoid(go) * torch.tanh(c)
+                hs.append(h)
+            vals[stg.out.root().id] = (torch.stack(hs, 1) if stg.seq else h).reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:
