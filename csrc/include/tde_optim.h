@@ -156,4 +156,72 @@ __device__ __forceinline__ void flat_apply(const FlatApply& f, long long t, int 
   }
 }
 
+// The deferred flush as ONE workgroup's work with a short dependent chain: the flag and, where the kind uses
+// it, the step counter first; then the ranges walked as one run of elements (a prefix over n[]), kFlushPer
+// elements per thread and pass, every load of a pass -- the weights, their slots and gradient replicas --
+// issued before the first wait (a thread past the end loads the last element again and stores nothing); every
+// store is predicated on the loaded flag instead of following a barrier behind it.
+// Same opt_lr_t / opt_step / flat_grad as flat_apply: the results are bit-identical.  Without `pend` the update
+// is unconditional.  Called by all `nt` threads of the workgroup (it holds a barrier); nothing else may write
+// the ranges, the flag or the replicas while it runs.
+// flat_flush's arithmetic, out of line: the flush is compiled into more than one kernel, and inlined into each
+// the compiler may contract opt_step's multiply-adds differently from one to the next (seen: momentum, one ulp).
+struct FlushStep { float w, m, v; };
+__device__ __noinline__ FlushStep flush_step(OptHyper h, float lr_t, float w, float g, float m, float v) {
+  FlushStep r;
+  r.m = m;
+  r.v = v;
+  r.w = opt_step(h, lr_t, w, g, r.m, r.v);
+  return r;
+}
+constexpr int kFlushThreads = 512;   // tde_flat_apply's workgroup
+constexpr int kFlushPer = 2;         // the small CNN's 320 conv elements are one pass of 256 threads too
+__device__ __forceinline__ void flat_flush(const FlatApply& f, int tid, int nt) {
+  const int go = f.pend ? *f.pend : 1;
+  const long long t = opt_uses_t(f.h.kind) ? *f.iterations : 0;
+  int total = 0;
+#pragma unroll
+  for (int k = 0; k < kFlatRanges; ++k) total += (k < f.nr && f.n[k] > 0) ? f.n[k] : 0;
+  for (int i0 = tid; i0 < total; i0 += kFlushPer * nt) {
+    int e[kFlushPer];
+    bool on[kFlushPer];
+    float w[kFlushPer], m[kFlushPer], v[kFlushPer], g[kFlushPer];
+#pragma unroll
+    for (int u = 0; u < kFlushPer; ++u) {
+      on[u] = i0 + u * nt < total;
+      const int i = on[u] ? i0 + u * nt : total - 1;
+      int o = i, lo = f.lo[0];   // element i of the run is element o of the range that starts at lo
+      bool in = false;           // ... found
+#pragma unroll
+      for (int k = 0; k + 1 < kFlatRanges; ++k) {
+        const int nk = f.n[k] > 0 ? f.n[k] : 0;
+        in = in || o < nk;
+        o = in ? o : o - nk;     // k + 1 < nr holds where it moves on: i < total
+        lo = in ? lo : f.lo[k + 1];
+      }
+      e[u] = lo + o;
+      w[u] = f.w[e[u]];
+      m[u] = opt_has_m(f.h.kind) ? f.m[e[u]] : 0.f;
+      v[u] = opt_has_v(f.h.kind) ? f.v[e[u]] : 0.f;
+      g[u] = flat_grad(f, e[u]);
+    }
+    const float lr_t = opt_lr_t(f.h, t);
+#pragma unroll
+    for (int u = 0; u < kFlushPer; ++u) {
+      const FlushStep s = flush_step(f.h, lr_t, w[u], g[u], m[u], v[u]);
+      if (go && on[u]) {
+        f.w[e[u]] = s.w;
+        flat_grad_zero(f, e[u]);
+        if (opt_has_m(f.h.kind)) f.m[e[u]] = s.m;
+        if (opt_has_v(f.h.kind)) f.v[e[u]] = s.v;
+      }
+    }
+  }
+  __syncthreads();   // every thread has its flag before thread 0 clears it
+  if (tid == 0 && go) {
+    if (f.pend) *f.pend = 0;
+    if (f.count) atomicAdd(f.count, 1ull);
+  }
+}
+
 }  // namespace tde

@@ -7,6 +7,7 @@
 // (csrc/data/pipeline.cpp) and ships S x B int32 row indices per execution; this kernel gathers the rows
 // into the training program's input ring.  dst[i] = src[idx[i]] for rows of `row_bytes` bytes.
 #include "tde_common.h"
+#include "tde_optim.h"
 
 namespace tde {
 
@@ -57,6 +58,7 @@ TDE_API int tde_gather_rows_dev(const void* src, long long row_bytes, long long 
 // moves 16-byte vectors when its size and pointers allow, 4-byte words otherwise.
 namespace tde {
 constexpr int kCopyPairs = 4;
+constexpr int kCopyThreads = 256;
 struct CopyPairs {
   const char* src[kCopyPairs];
   char* dst[kCopyPairs];
@@ -65,9 +67,18 @@ struct CopyPairs {
   int v16[kCopyPairs];
   int n;
 };
-__global__ __launch_bounds__(256) void copy_pairs_kernel(CopyPairs c) {
+// Copy workgroups [0, copy_blocks): one 16-byte unit per thread and pass.  FLUSH: one more workgroup, the last
+// block id, runs the deferred-update flush `f` (flat_flush) instead.  The copy never touches the flush's memory
+// and the flush never touches the pairs: nothing orders the two inside the launch.
+template <bool FLUSH>
+__global__ __launch_bounds__(kCopyThreads) void copy_pairs_kernel(CopyPairs c, int copy_blocks, FlatApply f) {
+  if (FLUSH && (int)blockIdx.x == copy_blocks) {
+    flat_flush(f, threadIdx.x, kCopyThreads);
+    return;
+  }
   const long long total = c.beg[c.n];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+  for (long long i = (long long)blockIdx.x * kCopyThreads + threadIdx.x; i < total;
+       i += (long long)copy_blocks * kCopyThreads) {
     int j = 0;
     while (j + 1 < c.n && i >= c.beg[j + 1]) ++j;
     const long long o = (i - c.beg[j]) * 16;   // byte offset of this thread's 16-byte unit in pair j
@@ -79,10 +90,16 @@ __global__ __launch_bounds__(256) void copy_pairs_kernel(CopyPairs c) {
     }
   }
 }
-}  // namespace tde
 
-TDE_API int tde_copy_pairs(int n, const void* const* src, void* const* dst, const long long* bytes, hipStream_t stream) {
+static int copy_pairs_launch(int n, const void* const* src, void* const* dst, const long long* bytes,
+                             const FlatApply* f, hipStream_t stream) {
   if (n < 1 || n > kCopyPairs) return -1;
+  if (f) {   // tde_flat_apply's refusals: nothing is launched, the copy included
+    if (!opt_kind_fused(f->h.kind)) return -3;
+    if (f->nr < 0 || f->nr > kFlatRanges || !opt_slots_ok(f->h.kind, f->m, f->v) ||
+        (opt_uses_t(f->h.kind) && !f->iterations))
+      return -3;
+  }
   CopyPairs c{};
   c.n = n;
   long long units = 0;
@@ -96,10 +113,27 @@ TDE_API int tde_copy_pairs(int n, const void* const* src, void* const* dst, cons
     units += (bytes[j] + 15) / 16;
   }
   c.beg[n] = units;
-  if (units == 0) return 0;
-  long long blocks = (units + 255) / 256;
+  if (units == 0 && !f) return 0;
+  long long blocks = (units + kCopyThreads - 1) / kCopyThreads;
   blocks = blocks > 2048 ? 2048 : blocks;
-  copy_pairs_kernel<<<(int)blocks, 256, 0, stream>>>(c);
+  const int cb = (int)blocks;
+  if (f)
+    copy_pairs_kernel<true><<<cb + 1, kCopyThreads, 0, stream>>>(c, cb, *f);
+  else
+    copy_pairs_kernel<false><<<cb, kCopyThreads, 0, stream>>>(c, cb, FlatApply{});
   TDE_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace tde
+
+TDE_API int tde_copy_pairs(int n, const void* const* src, void* const* dst, const long long* bytes, hipStream_t stream) {
+  return copy_pairs_launch(n, src, dst, bytes, nullptr, stream);
+}
+
+// tde_copy_pairs with, when `f` is given, the deferred-update flush `f` (tde_flat_apply in its `pend` form, or
+// unconditional without one) in the same launch: one more workgroup.  f == nullptr: tde_copy_pairs.  A kind
+// the flush does not know, missing slots or too many ranges: -3, nothing launched.
+TDE_API int tde_copy_pairs_apply(int n, const void* const* src, void* const* dst, const long long* bytes,
+                                 const tde::FlatApply* f, hipStream_t stream) {
+  return copy_pairs_launch(n, src, dst, bytes, f, stream);
 }

@@ -281,16 +281,16 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const float* w, bf1
   }
 }
 
-// Deferred-update flush (one workgroup): applies the ranges if *pend with t = *iterations, then clears
-// *pend.  Without pend (an unconditional update) the ranges are spread over the whole grid.
-__global__ __launch_bounds__(256) void flat_apply_kernel(FlatApply f) {
-  __shared__ int go;
-  if (threadIdx.x == 0) go = f.pend ? *f.pend : 1;
-  __syncthreads();
-  if (!go) return;
-  flat_apply(f, opt_uses_t(f.h.kind) ? *f.iterations : 0, blockIdx.x * 256 + threadIdx.x, 256 * gridDim.x);
-  __syncthreads();
-  if (threadIdx.x == 0 && f.pend) *f.pend = 0;
+// Deferred-update flush (one workgroup of kFlushThreads, flat_flush): applies the ranges if *pend with
+// t = *iterations, then clears *pend.  Without pend (an unconditional update) the ranges are spread over the
+// whole grid.
+__global__ __launch_bounds__(kFlushThreads) void flat_apply_kernel(FlatApply f) {
+  if (f.pend) {
+    flat_flush(f, threadIdx.x, blockDim.x);
+    return;
+  }
+  flat_apply(f, opt_uses_t(f.h.kind) ? *f.iterations : 0, blockIdx.x * blockDim.x + threadIdx.x,
+             blockDim.x * gridDim.x);
   if (threadIdx.x == 0 && blockIdx.x == 0 && f.count) atomicAdd(f.count, 1ull);
 }
 
@@ -315,7 +315,7 @@ TDE_API int tde_flat_apply(float* w, float* g, float* m, float* v, const long lo
   for (int i = 0; i < nr; ++i) maxn = f.n[i] > maxn ? f.n[i] : maxn;
   // pend: one workgroup (it reads and clears the flag); otherwise about one element per thread
   const int nb = pend ? 1 : (maxn + 255) / 256 < 1 ? 1 : ((maxn + 255) / 256 > 64 ? 64 : (maxn + 255) / 256);
-  flat_apply_kernel<<<nb, 256, 0, stream>>>(f);
+  flat_apply_kernel<<<nb, pend ? kFlushThreads : 256, 0, stream>>>(f);
   TDE_LAUNCH_CHECK();
   return 0;
 }

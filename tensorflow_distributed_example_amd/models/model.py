@@ -190,8 +190,15 @@ class Model:
         for prog in self._programs.values():
             prog.on_weights_loaded()
 
+    def _flush_programs(self):
+        """Updates a training program's last replay left due (``Program.flush``), before the weights are read
+        or replaced from outside the programs."""
+        for prog in self._programs.values():
+            prog.flush()
+
     def _sync_on_read(self):
         """MEAN of the SyncOnRead (BN moving-stat) variables across replicas (C4)."""
+        self._flush_programs()
         st = self._strategy
         lst = self._stores.get(id(st)) if st is not None else None
         has_state = any(not seg.trainable for seg in self._store.segments.values())
@@ -255,6 +262,7 @@ class Model:
         specs = self._spec_list()
         if len(weights) != len(specs):
             raise ValueError(f"expected {len(specs)} arrays, got {len(weights)}")
+        self._flush_programs()
         self._store.load_dict({s.full_name: w for s, w in zip(specs, weights)})
         self._weights_changed()
 
@@ -271,6 +279,7 @@ class Model:
         return out
 
     def load_state_dict(self, d, strict=True):
+        self._flush_programs()
         self._store.load_dict(d, strict=strict)
         self._weights_changed()
 

@@ -146,6 +146,17 @@ def flat_apply(spec: FlatApply):
     N.check(rc, "tde_flat_apply")
 
 
+def copy_pairs_apply(pairs, spec: FlatApply | None = None, device=None):
+    """The staging copy of ``pairs`` = [(src, dst), ...] (device tensors; each ``src`` whole into the front of
+    its ``dst``) and, with ``spec``, that deferred-update flush (``flat_apply``) in the same launch."""
+    n = len(pairs)
+    rc = N.hip().tde_copy_pairs_apply(
+        n, (_ct.c_void_p * n)(*[s.data_ptr() for s, _ in pairs]), (_ct.c_void_p * n)(*[d.data_ptr() for _, d in pairs]),
+        (_ct.c_longlong * n)(*[s.numel() * s.element_size() for s, _ in pairs]),
+        _ct.byref(spec) if spec is not None else None, N.stream_ptr(device))
+    N.check(rc, "tde_copy_pairs_apply")
+
+
 def _s():
     return N.stream_ptr()
 

@@ -230,6 +230,19 @@ class ReplicaPlan:
     def finish(self):
         """End of an execution (a run of steps): commit deferred updates."""
 
+    # A plan whose ``finish()`` is one flush launch can leave it out of the captured execution: the Program
+    # replays the steps alone, marks the flush due, and hands it to the next staging copy's launch
+    # (``take_flush``) or issues it (``flush``) before anything else may read or write what it updates.
+    flush_due = False
+    defers_flush = False
+
+    def take_flush(self):
+        """The due flush's descriptor for a launch that carries it, the flag cleared; None if none is due."""
+        return None
+
+    def flush(self):
+        """Issue the flush if it is due."""
+
     def trace_tensors(self):
         """State recorded per step by ``Program.enable_trace`` (diagnostics)."""
         return [self.store.w, self.metrics]
@@ -815,16 +828,35 @@ class SmallCnnPlan(ReplicaPlan):
     def finish(self):
         if self.step_mode == "local":
             # only the last step's conv update can be pending (each backward commits the previous one)
-            self.K.flat_apply(self._flush[1 - self.parity])
+            self.flush_due = True
+            self.flush()
+
+    @property
+    def defers_flush(self):
+        return self.step_mode == "local" and self._flush is not None
+
+    def take_flush(self):
+        if not self.flush_due:
+            return None
+        self.flush_due = False
+        return self._flush[1 - self.parity]
+
+    def flush(self):
+        f = self.take_flush()
+        if f is not None:
+            with torch.cuda.device(self.device):
+                self.K.flat_apply(f)
 
     def step_invariants(self):
         """The deferred conv update's state between executions (step mode "local"; synchronises): nothing
         pending, every gradient replica consumed."""
+        self.flush()
         torch.cuda.synchronize(self.device)
         return dict(pending=[int(v) for v in self.pend.cpu()], gconv_abs_max=float(self.gconv.abs().max()))
 
     def on_weights_loaded(self):
         # loaded weights replace whatever update was outstanding
+        self.flush_due = False
         self.pend.zero_()
         self.gconv.zero_()
         self.store.g.zero_()
@@ -930,6 +962,7 @@ class ConvNetPlan(SmallCnnPlan):
         return [(seg[self.names[k]].offset, seg[self.names[k]].numel) for k in ("wc", "bc")]
 
     def set_step_mode(self, mode):
+        self.flush()   # a due flush belongs to the descriptors that are about to go
         super().set_step_mode(mode)
         if mode != self._mode_set:
             self.gconv.zero_()   # the replicas change roles between the step modes
@@ -1087,6 +1120,7 @@ class ConvNetGenPlan(SmallCnnPlan):
         self._xg_rep = self.crep > 1
 
     def set_step_mode(self, mode):
+        self.flush()   # a due flush belongs to the descriptors that are about to go
         super().set_step_mode(mode)
         self._copt = self._fly = self._hopt = self._commit = self._flush = None
         self.gconv.zero_()

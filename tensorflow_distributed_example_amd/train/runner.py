@@ -12,7 +12,6 @@ device ring buffers [S, B, ...] filled by one async H2D (or D2D) copy.
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import os
 import time
 
@@ -20,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _native as N
+from ..ops import kernels as K
 from . import program as PG
 
 
@@ -306,17 +306,17 @@ class Program:
             with _ctx(self.devices[r]):
                 xr, yr = self.x_ring[r], self.y_ring[r]
                 if self.aug is not None:
+                    self.plans[r].flush()
                     self.x_stage[r].stage(x, self._aug_src[r])
                     self.y_stage[r].stage(y, yr)
                     self._augment(r, self.S * self.B, self.B, step0)
                     continue
                 if _same_device_pair(x, xr) and _same_device_pair(y, yr):
-                    # a device-resident batch group: x and y into the ring in ONE copy launch
-                    N.check(N.hip().tde_copy_pairs(
-                        2, (C.c_void_p * 2)(x.data_ptr(), y.data_ptr()), (C.c_void_p * 2)(xr.data_ptr(), yr.data_ptr()),
-                        (C.c_longlong * 2)(x.numel() * x.element_size(), y.numel() * y.element_size()),
-                        N.stream_ptr(xr.device)), "tde_copy_pairs")
+                    # a device-resident batch group: x and y into the ring in ONE copy launch, which also
+                    # carries the flush the last replay left due
+                    K.copy_pairs_apply([(x, xr), (y, yr)], self.plans[r].take_flush(), xr.device)
                     continue
+                self.plans[r].flush()
                 self.x_stage[r].stage(x, xr)
                 self.y_stage[r].stage(y, yr)
 
@@ -414,12 +414,27 @@ class Program:
                 yield
             cur.wait_stream(s)
 
-    def _finish(self):
+    def _finish(self, defer=False):
+        """``defer``: a plan that can leave its flush to the launches after the execution does so."""
         for plan in self.plans:
+            if defer and plan.defers_flush:
+                continue
             with _ctx(plan.device):
                 plan.finish()
 
-    def _steps(self, S, B=None):
+    def flush(self):
+        """Issue what the last replay left due (``ReplicaPlan.flush_due``).  Everything that may follow a replay
+        and is not the staging copy that carries the flush comes through here first."""
+        for plan in self.plans:
+            plan.flush()
+
+    def _flush_model(self):
+        """``flush`` of the model's other programs: they share this program's weights."""
+        for prog in getattr(self.model, "_programs", {}).values():
+            if prog is not self:
+                prog.flush()
+
+    def _steps(self, S, B=None, defer=False):
         if self.per_replica:
             for gi in range(len(self.groups)):
                 with self._on_group(gi):
@@ -436,7 +451,7 @@ class Program:
             self._reduce_and_apply()
             if self._trace is not None:
                 self._record(s)
-        self._finish()
+        self._finish(defer)
 
     def enable_trace(self):
         """Diagnostics: after every step of an execution, copy each plan's ``trace_tensors()`` (weights and
@@ -444,12 +459,17 @@ class Program:
         so an execution's per-step states are readable after it (``sync()`` first).  Single-group layouts."""
         if self.per_replica:
             raise NotImplementedError("per-step traces are recorded for single-group layouts")
+        self.flush()
         self.graphs = {}
         self._trace = []
         for p in self.plans:
             n = sum(t.numel() for t in p.trace_tensors())
             self._trace.append(torch.zeros(self.S, n, dtype=torch.float32, device=p.device))
-        self.trace = self._trace
+
+    @property
+    def trace(self):
+        self.flush()
+        return self._trace
 
     def _record(self, s):
         for r, p in enumerate(self.plans):
@@ -551,7 +571,7 @@ class Program:
             gc.disable()
             try:
                 with torch.cuda.graph(g):
-                    self._steps(self.S)
+                    self._steps(self.S, defer=True)   # the flush follows the replay (``run``)
             finally:
                 gc.enable()
                 self._end = self._parities()
@@ -563,6 +583,7 @@ class Program:
         self.graph = g
 
     def run(self):
+        self.flush()
         if self.use_graph:
             if self._graph_key != self.model.optimizer.key():
                 self.graphs = {}
@@ -600,6 +621,7 @@ class Program:
                     g.replay()
             for p, q in zip(self.plans, end):
                 p.parity = q
+                p.flush_due = not self.per_replica and p.defers_flush
         else:
             self._warm_comm()
             for p in self.plans:
@@ -609,6 +631,7 @@ class Program:
     def run_single(self, per_replica, global_actual, step0=0):
         """One (possibly partial) step executed eagerly. per_replica[r] = (x[B_r,...], y[B_r]); ``step0``: its
         global step (the input stage draws by it, with the batch's own row count)."""
+        self.flush()
         self._warm_comm()
         for r, (x, y) in enumerate(per_replica):
             with _ctx(self.devices[r]):
@@ -674,6 +697,8 @@ class Program:
 
     # ------------------------------------------------------------------ eval / predict
     def eval_batch(self, per_replica):
+        self.flush()
+        self._flush_model()
         for r, (x, y) in enumerate(per_replica):
             n = len(y)
             if n == 0:
@@ -686,6 +711,8 @@ class Program:
 
     def predict_batch(self, x):
         n = len(x)
+        self.flush()
+        self._flush_model()
         with _ctx(self.devices[0]):
             self.x_stage[0].stage(x, self.x_ring[0][0])
             out = self.plans[0].predict(self.x_ring[0][0], n)
@@ -693,10 +720,12 @@ class Program:
 
     # ------------------------------------------------------------------ metrics
     def reset_metrics(self):
+        self.flush()
         for p in self.plans:
             p.reset_metrics()
 
     def local_metrics(self):
+        self.flush()
         acc = None
         for p in self.plans:
             m = p.all_metrics().detach().double().cpu()
@@ -707,6 +736,7 @@ class Program:
         """SUM of the metric accumulators over ALL replicas (SyncOnRead SUM, C3/C5)."""
         if self.comm is None:
             return self.local_metrics()
+        self.flush()
         self.comm.check_health()   # surfaces a timed-out peer wait of the xGMI all-reduce
         bufs = [p.all_metrics().clone() for p in self.plans]   # both accumulators in one all-reduce
         self.comm.all_reduce_(bufs)
@@ -716,12 +746,14 @@ class Program:
         return bufs[0].double().cpu()
 
     def on_weights_loaded(self):
+        self._flush_model()   # the loaded weights replace this program's own outstanding update, not the others'
         for p in self.plans:
             p._reg_stale = True   # the regularizers' penalty is computed again at the next evaluation batch
             with _ctx(p.device):
                 p.on_weights_loaded()
 
     def sync(self):
+        self.flush()
         for d in self.devices:
             if d.type == "cuda":
                 torch.cuda.synchronize(d)
