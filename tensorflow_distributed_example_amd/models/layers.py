@@ -887,6 +887,95 @@ class LSTM(Layer):
                     **_reg_config(self, "kernel_regularizer", "recurrent_regularizer", "bias_regularizer"))
 
 
+class GRU(Layer):
+    """Keras ``GRU`` in its default ``reset_after=True`` form on [N, T, D]: the last h [N, units], or every h
+    [N, T, units] with ``return_sequences``.  From a zero state, with X_t = x_t W + b[0] and R_t = h_{t-1} U + b[1]
+    in Keras's gate order z, r, h along the 3*units axis:
+        z = sigmoid(X_z + R_z);  r = sigmoid(X_r + R_r);  hh = tanh(X_h + r * R_h)
+        h_t = z * h_{t-1} + (1 - z) * hh
+    Weights under Keras's nested names: ``gru_cell/kernel`` [D, 3u], ``gru_cell/recurrent_kernel`` [u, 3u],
+    ``gru_cell/bias`` [2, 3u] (row 0 the input bias, row 1 the recurrent bias).  ``reset_after=False``, other
+    activations, dropout, masks, initial and returned state, ``go_backwards``, ``stateful`` and ``unroll`` are
+    refused.  On the GPU: a 1x1 GEMM stage for x W + b[0] over all N*T tokens, then the resident sweep of
+    csrc/kernels/gru.hip (float32 policy)."""
+    _prefix = "gru"
+
+    def __init__(self, units, activation="tanh", recurrent_activation="sigmoid", use_bias=True,
+                 kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
+                 kernel_regularizer=None, recurrent_regularizer=None, bias_regularizer=None, dropout=0.0,
+                 recurrent_dropout=0.0, return_sequences=False, return_state=False, go_backwards=False,
+                 stateful=False, unroll=False, reset_after=True, **kw):
+        super().__init__(**kw)
+        for arg, val, ok in (("reset_after", reset_after, bool(reset_after)),
+                             ("activation", activation, activation == "tanh"),
+                             ("recurrent_activation", recurrent_activation, recurrent_activation == "sigmoid"),
+                             ("dropout", dropout, dropout == 0), ("recurrent_dropout", recurrent_dropout,
+                                                                  recurrent_dropout == 0),
+                             ("return_state", return_state, not return_state),
+                             ("go_backwards", go_backwards, not go_backwards), ("stateful", stateful, not stateful),
+                             ("unroll", unroll, not unroll)):
+            if not ok:
+                raise NotImplementedError(f"GRU: {arg}={val!r} is not supported")
+        self.units = int(units)
+        if self.units < 1:
+            raise ValueError(f"GRU: units={units!r}")
+        self.use_bias = use_bias
+        self.return_sequences = bool(return_sequences)
+        self.kernel_initializer, self.recurrent_initializer = kernel_initializer, recurrent_initializer
+        self.bias_initializer = bias_initializer
+        self.kernel_regularizer = regularizers.get(kernel_regularizer)
+        self.recurrent_regularizer = regularizers.get(recurrent_regularizer)
+        self.bias_regularizer = regularizers.get(bias_regularizer)
+
+    def __call__(self, inputs, mask=None, training=None, initial_state=None):
+        for arg, val in (("mask", mask), ("initial_state", initial_state)):
+            if val is not None:
+                raise NotImplementedError(f"{self.name} (GRU): {arg}= is not supported: whole sequences from a "
+                                          "zero state only")
+        return super().__call__(inputs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 2:
+            raise ValueError(f"{self.name}: input [N, T, D] expected, got {(None,) + tuple(input_shape)}")
+        u = self.units
+        self.add_weight("gru_cell/kernel", (input_shape[-1], 3 * u), self.kernel_initializer,
+                        regularizer=self.kernel_regularizer)
+        self.add_weight("gru_cell/recurrent_kernel", (u, 3 * u), self.recurrent_initializer,
+                        regularizer=self.recurrent_regularizer)
+        if self.use_bias:
+            self.add_weight("gru_cell/bias", (2, 3 * u), self.bias_initializer, regularizer=self.bias_regularizer)
+        self.built = True
+
+    def compute_output_shape(self, s):
+        return (s[0], self.units) if self.return_sequences else (self.units,)
+
+    @staticmethod
+    def recurrence(X, U, rb, return_sequences):
+        """The step loop over the projected input X [N, T, 3u] with the recurrent kernel U [u, 3u] and the
+        recurrent bias rb [3u] (or None): every h [N, T, u], or the last [N, u]."""
+        u = U.shape[0]
+        h = X.new_zeros(X.shape[0], u)
+        hs = []
+        for t in range(X.shape[1]):
+            R = h @ U if rb is None else h @ U + rb
+            (xz, xr, xh), (rz, rr, rh) = X[:, t].split(u, dim=-1), R.split(u, dim=-1)
+            z, r = torch.sigmoid(xz + rz), torch.sigmoid(xr + rr)
+            h = z * h + (1 - z) * torch.tanh(xh + r * rh)
+            hs.append(h)
+        return torch.stack(hs, 1) if return_sequences else h
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        X, b = x @ W["gru_cell/kernel"], W["gru_cell/bias"] if self.use_bias else None
+        if b is not None:
+            X = X + b[0]
+        return self.recurrence(X, W["gru_cell/recurrent_kernel"], None if b is None else b[1], self.return_sequences)
+
+    def get_config(self):
+        return dict(name=self.name, units=self.units, use_bias=self.use_bias, reset_after=True,
+                    return_sequences=self.return_sequences,
+                    **_reg_config(self, "kernel_regularizer", "recurrent_regularizer", "bias_regularizer"))
+
+
 class Add(Layer):
     """Element-wise sum of same-shaped inputs (ResNet shortcut join)."""
     _prefix = "add"
@@ -1066,7 +1155,7 @@ class RandomZoom(_RandomAffine):
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, GroupNormalization,
-                                         LayerNormalization, MultiHeadAttention, LSTM, Add, RandomFlip,
+                                         LayerNormalization, MultiHeadAttention, LSTM, GRU, Add, RandomFlip,
                                          RandomTranslation, RandomRotation, RandomZoom]}
 
 

@@ -163,6 +163,17 @@ def mnist_lstm(name=None):
     ], name=name)
 
 
+def mnist_gru(name=None):
+    """The twin of ``mnist_lstm`` on the other recurrent layer: two stacked GRU(64), the first returning its
+    sequence, then the classifier (runs on the float32 layer-wise plan; csrc/kernels/gru.hip)."""
+    return Sequential([
+        L.Reshape((28, 28), input_shape=(28, 28, 1)),
+        L.GRU(64, return_sequences=True),
+        L.GRU(64),
+        L.Dense(10),
+    ], name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

@@ -49,6 +49,9 @@ N.register_hip({
     # csrc/kernels/lstm.hip
     "tde_lstm32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),   # z, U, hseq, hprev, gates, cseq, hlast, B, T, u
     "tde_lstm32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),         # gates, cseq, U, dh, dz, B, T, u, last_only
+    # csrc/kernels/gru.hip
+    "tde_gru32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),   # x, U, rb, hseq, hprev, acts, hlast, B, T, u
+    "tde_gru32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),    # acts, hprev, U, dh, dx, dr, B, T, u, last_only
 })
 
 _NODROP = DropSpec()
@@ -398,6 +401,42 @@ def lstm_bwd(gates, cseq, rk, dh, dz, B, T, units, last_only):
         _f32(t, k, f"lstm_bwd {what}")
     N.check(N.hip().tde_lstm32_bwd(_P(gates), _P(cseq), _P(rk), _P(dh), _P(dz), B, T, units, int(bool(last_only)),
                                    _s()), "tde_lstm32_bwd")
+
+
+# ---------------------------------------------------------------- GRU recurrence (csrc/kernels/gru.hip)
+def gru_check(B, T, units, what):
+    """The supported range of csrc/kernels/gru.hip, which is that of the LSTM sweeps: B sequences of T steps,
+    ``units`` hidden units.  Returns the element count of a [B, T, units] tensor."""
+    return lstm_check(B, T, units, what)
+
+
+def gru_fwd(x, rk, rb, hseq, hprev, acts, B, T, units, hlast=None):
+    """The forward sweep over x = input W + b[0] [B, T, 3 units] (gate order z, r, h) with the recurrent kernel rk
+    [units, 3 units] and the recurrent bias rb [3 units] (None: none) from a zero state: hseq (h_t) and hprev
+    (h_{t-1}, zeros at t = 0) [B, T, units], ``acts`` [B, T, 4 units] in the order z, r, hh, R_h (the candidate's
+    recurrent pre-activation h_{t-1} U_h + rb_h), and the last h into ``hlast`` [B, units] when given."""
+    n = gru_check(B, T, units, "gru_fwd")
+    for t, k, what in ((x, 3 * n, "x"), (rk, 3 * units * units, "recurrent kernel"), (hseq, n, "hseq"),
+                       (hprev, n, "hprev"), (acts, 4 * n, "acts")):
+        _f32(t, k, f"gru_fwd {what}")
+    if rb is not None:
+        _f32(rb, 3 * units, "gru_fwd recurrent bias")
+    if hlast is not None:
+        _f32(hlast, B * units, "gru_fwd hlast")
+    N.check(N.hip().tde_gru32_fwd(_P(x), _P(rk), _P(rb), _P(hseq), _P(hprev), _P(acts), _P(hlast), B, T, units,
+                                  _s()), "tde_gru32_fwd")
+
+
+def gru_bwd(acts, hprev, rk, dh, dx, dr, B, T, units, last_only):
+    """dx and dr [B, T, 3 units] = the gradients of ``gru_fwd``'s x and of the recurrent pre-activation
+    h_{t-1} rk + rb (they differ in the candidate's block) under dh, the gradient of hseq [B, T, units] or, with
+    ``last_only``, of the last h alone [B, units].  One launch, no atomics: bitwise reproducible."""
+    n = gru_check(B, T, units, "gru_bwd")
+    for t, k, what in ((acts, 4 * n, "acts"), (hprev, n, "hprev"), (rk, 3 * units * units, "recurrent kernel"),
+                       (dh, B * units if last_only else n, "dh"), (dx, 3 * n, "dx"), (dr, 3 * n, "dr")):
+        _f32(t, k, f"gru_bwd {what}")
+    N.check(N.hip().tde_gru32_bwd(_P(acts), _P(hprev), _P(rk), _P(dh), _P(dx), _P(dr), B, T, units,
+                                  int(bool(last_only)), _s()), "tde_gru32_bwd")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

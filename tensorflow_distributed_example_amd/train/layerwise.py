@@ -273,6 +273,19 @@ class LayerwisePlan(PG.ReplicaPlan):
                                     names=("lstm_cell/kernel", "lstm_cell/bias")))
                 stages.append(_Lstm(self, layer, z, tout))
                 continue
+            if isinstance(layer, L.GRU):
+                # as for an LSTM: x W + b[0] as one 1x1 GEMM stage into an internal tensor (row 0 of the bias is
+                # that stage's), then the recurrence with row 1 (csrc/kernels/gru.hip)
+                if not self.f32:
+                    raise Unsupported(f"{layer.name} (GRU): the recurrence kernels are float32 only; the "
+                                      "mixed_bfloat16 policy has none")
+                z = _T(max(T) + 1, (tin[0].shape[0], 3 * layer.units))
+                z.producer, z.consumers = i, [i]
+                T[z.id] = z
+                stages.append(_Gemm(self, layer, tin[0], z, False, pointwise=True,
+                                    names=("gru_cell/kernel", "gru_cell/bias"), bias_row=0))
+                stages.append(_Gru(self, layer, z, tout))
+                continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
@@ -492,11 +505,12 @@ class LayerwisePlan(PG.ReplicaPlan):
 
 # ---------------------------------------------------------------------------------------
 class _Gemm(_Stage):
-    def __init__(self, plan, layer, tin, tout, stats, pointwise=False, names=None):
+    def __init__(self, plan, layer, tin, tout, stats, pointwise=False, names=None, bias_row=None):
         """``pointwise``: a 1x1 / stride-1 / unpadded step of a composite layer on the token grid of ``tin``
         (float32 plans: the stages around it exist there only).  ``names``: the layer's (kernel, bias) variables
         the step runs on, any shape that flattens to [C, Co] and [Co] — default: a SeparableConv2D's
-        ``pointwise_kernel`` and ``bias``, with the layer's activation; a named step has none."""
+        ``pointwise_kernel`` and ``bias``, with the layer's activation; a named step has none.  ``bias_row``: the
+        step's bias and its gradient are that row of a [rows, Co] bias variable (a GRU's input bias)."""
         self.layer, self.inp, self.out = layer, tin, tout
         self.node_index = tout.producer
         self.stats = stats
@@ -509,6 +523,9 @@ class _Gemm(_Stage):
         self.gW = st.grad(self.wname)
         self.b = st.view(self.bname) if self.bname else None
         self.gb = st.grad(self.bname) if self.bname else None
+        self.bias_row = bias_row
+        if self.bname and bias_row is not None:
+            self.b, self.gb = self.b[bias_row], self.gb.view(self.b.shape)[bias_row]
         self.conv = pointwise or isinstance(layer, L.Conv2D)
         need_dgrad = tin.root().id != 0
         self.need_dgrad = need_dgrad
@@ -1129,6 +1146,65 @@ class _Lstm(_Stage):
         O32.dense_wgrad(self.hprev, dz, self.gU.view(self.units, -1), B * self.T, part=p.wpart)
 
 
+class _Gru(_Stage):
+    """The recurrence of a GRU on csrc/kernels/gru.hip — float32 forms only — over the internal tensor
+    X = x W + b[0] [T, 3 units] that the projection stage wrote.  The stage owns what the forward saves: hprev
+    (h_{t-1} per token, the left operand of dU), the activations z, r, hh with R_h and, unless the layer returns
+    its sequence (then the output tensor is hseq), hseq.  The recurrent bias, row 1 of ``gru_cell/bias``, is
+    this stage's: the kernel reads it, and its gradient is the column sum of dR over the B*T tokens, through the
+    ordered reduction of a Dense bias gradient.  The backward sweep writes X.grad, the projection stage's output
+    gradient (which yields dW, db[0] and dx there), and dR; dU = hprev^T dR is one weight-gradient GEMM.  The bias
+    variable counts as the projection stage's: that one runs later in the backward and so completes it.
+    Geometry: (B, T, units)."""
+
+    def __init__(self, plan, layer, z, tout):
+        self.layer, self.inp, self.out = layer, z, tout
+        self.node_index = tout.producer
+        self.T, self.units, self.seq = z.shape[0], layer.units, layer.return_sequences
+        try:
+            O32.gru_check(*self.geom(plan.B), f"{layer.name} (GRU)")
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        self.uname = f"{layer.name}/gru_cell/recurrent_kernel"
+        self.U = plan.store.view(self.uname)
+        self.gU = plan.store.grad(self.uname)
+        self.bname = f"{layer.name}/gru_cell/bias" if layer.use_bias else None
+        self.rb = plan.store.view(self.bname)[1] if self.bname else None
+        self.grb = plan.store.grad(self.bname).view(2, -1)[1] if self.bname else None
+
+    def geom(self, B):
+        return (B, self.T, self.units)
+
+    def param_names(self):
+        return [self.uname]
+
+    def alloc(self, B, dev):
+        n = B * self.T * self.units
+        self.hprev = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.acts = torch.zeros(4 * n, dtype=torch.float32, device=dev)
+        self.dr = torch.zeros(3 * n, dtype=torch.float32, device=dev)
+        self.hseq = None if self.seq else torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def wpart_need(self, B):
+        return O32.wgrad_part_elems(self.units, 3 * self.units, B * self.T)
+
+    def grad_inputs(self):
+        return [self.inp]
+
+    def fwd(self, p, B, training, mode="train"):
+        out = self.out.root().buf
+        O32.gru_fwd(self.inp.root().buf, self.U, self.rb, out if self.seq else self.hseq, self.hprev, self.acts,
+                    *self.geom(B), hlast=None if self.seq else out)
+
+    def bwd(self, p, B):
+        dx = self.inp.root().grad   # X has this one consumer: written, never accumulated
+        O32.gru_bwd(self.acts, self.hprev, self.U, self.out.root().grad, dx, self.dr, *self.geom(B),
+                    last_only=not self.seq)
+        O32.dense_wgrad(self.hprev, self.dr, self.gU.view(self.units, -1), B * self.T, part=p.wpart)
+        if self.grb is not None:
+            O32.act_bwd(self.dr, None, B * self.T, 3 * self.units, relu=False, dbias=self.grb)
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
@@ -1391,7 +1467,7 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             else:
                 o = a.reshape(-1, a.shape[-1]) @ qw(stg.wname)
             if stg.bname:
-                o = o + W[stg.bname].reshape(-1)
+                o = o + (W[stg.bname].reshape(-1) if stg.bias_row is None else W[stg.bname][stg.bias_row])
             if stg.relu:
                 o = F.relu(o)
             vals[stg.out.root().id] = QR(o.reshape(B, -1))
@@ -1423,6 +1499,9 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
                 h = torch.sigmoid(go) * torch.tanh(c)
                 hs.append(h)
             vals[stg.out.root().id] = (torch.stack(hs, 1) if stg.seq else h).reshape(B, -1)
+        elif isinstance(stg, _Gru):
+            rb = W[stg.bname][1] if stg.bname else None
+            vals[stg.out.root().id] = L.GRU.recurrence(get(stg.inp), W[stg.uname], rb, stg.seq).reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:
