@@ -59,6 +59,11 @@ def _truncated_normal(shape, gen, std):
     return (x * std).float()
 
 
+def uniform(shape, gen):
+    """Keras ``RandomUniform`` at its defaults, [-0.05, 0.05): the ``Embedding`` default."""
+    return (torch.rand(shape, generator=gen, dtype=torch.float64) * 2 - 1).mul_(0.05).float()
+
+
 def zeros(shape, gen=None):
     return torch.zeros(shape)
 
@@ -80,7 +85,7 @@ def orthogonal(shape, gen):
 
 _REG = {
     "glorot_uniform": glorot_uniform, "glorot_normal": glorot_normal, "he_normal": he_normal,
-    "he_uniform": he_uniform, "zeros": zeros, "ones": ones, "orthogonal": orthogonal,
+    "he_uniform": he_uniform, "uniform": uniform, "zeros": zeros, "ones": ones, "orthogonal": orthogonal,
 }
 
 

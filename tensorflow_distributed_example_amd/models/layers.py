@@ -469,6 +469,31 @@ class GlobalAveragePooling2D(Layer):
         return x.mean(dim=(1, 2))
 
 
+class GlobalAveragePooling1D(Layer):
+    """[N, T, C] -> [N, C]: the mean over the steps (``tde_gap32`` with HW = T on the GPU)."""
+    _prefix = "global_average_pooling1d"
+
+    def __init__(self, data_format=None, keepdims=False, **kw):
+        super().__init__(**kw)
+        if keepdims:
+            raise NotImplementedError("GlobalAveragePooling1D: keepdims=True is not supported")
+        if data_format not in (None, "channels_last"):
+            raise NotImplementedError(f"GlobalAveragePooling1D: data_format={data_format!r} is not supported")
+
+    def __call__(self, inputs, mask=None):
+        if mask is not None:
+            raise NotImplementedError(f"{self.name} (GlobalAveragePooling1D): mask= is not supported")
+        return super().__call__(inputs)
+
+    def compute_output_shape(self, s):
+        if len(s) != 2:
+            raise ValueError(f"{self.name}: input [N, T, C] expected, got {(None,) + tuple(s)}")
+        return (s[-1],)
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        return x.mean(dim=1)
+
+
 class ZeroPadding2D(Layer):
     _prefix = "zero_padding2d"
 
@@ -976,6 +1001,60 @@ class GRU(Layer):
                     **_reg_config(self, "kernel_regularizer", "recurrent_regularizer", "bias_regularizer"))
 
 
+class Embedding(Layer):
+    """Keras ``Embedding``: integer ids [N, T] -> [N, T, output_dim], rows of the one variable ``embeddings``
+    [input_dim, output_dim].  Ids arrive as the model input (float32 on the device, truncated toward zero as Keras
+    casts them to int32); an id outside [0, input_dim) gives a zero row and no gradient, as TensorFlow's GPU
+    gather.  ``mask_zero``, ``embeddings_constraint``, ``sparse`` and ``lora_rank`` are refused.  On the GPU:
+    the gather and the ordered scatter-sum of csrc/kernels/embedding.hip (float32 policy), first layer only."""
+    _prefix = "embedding"
+
+    def __init__(self, input_dim, output_dim, embeddings_initializer="uniform", embeddings_regularizer=None,
+                 embeddings_constraint=None, mask_zero=False, input_length=None, sparse=False, lora_rank=None,
+                 **kw):
+        if input_length is not None and kw.get("input_shape") is None:
+            kw["input_shape"] = (int(input_length),)
+        super().__init__(**kw)
+        for arg, val, ok in (("mask_zero", mask_zero, not mask_zero),
+                             ("embeddings_constraint", embeddings_constraint, embeddings_constraint is None),
+                             ("sparse", sparse, not sparse), ("lora_rank", lora_rank, lora_rank is None)):
+            if not ok:
+                raise NotImplementedError(f"Embedding: {arg}={val!r} is not supported")
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        if min(self.input_dim, self.output_dim) < 1:
+            raise ValueError(f"Embedding: input_dim={input_dim!r}, output_dim={output_dim!r}")
+        self.input_length = None if input_length is None else int(input_length)
+        self.embeddings_initializer = embeddings_initializer
+        self.embeddings_regularizer = regularizers.get(embeddings_regularizer)
+
+    def build(self, input_shape):
+        if len(input_shape) != 1:
+            raise ValueError(f"{self.name}: input [N, T] expected, got {(None,) + tuple(input_shape)}")
+        self.add_weight("embeddings", (self.input_dim, self.output_dim), self.embeddings_initializer,
+                        regularizer=self.embeddings_regularizer)
+        self.built = True
+
+    def compute_output_shape(self, s):
+        return (s[0], self.output_dim)
+
+    @staticmethod
+    def lookup(ids, table):
+        """table[ids] with the ids truncated toward zero and zero rows for those outside the table."""
+        ids = ids.long()
+        ok = (ids >= 0) & (ids < table.shape[0])
+        return F.embedding(ids.clamp(0, table.shape[0] - 1), table) * ok.unsqueeze(-1).to(table.dtype)
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        return self.lookup(x, W["embeddings"])
+
+    def get_config(self):
+        cfg = dict(name=self.name, input_dim=self.input_dim, output_dim=self.output_dim,
+                   **_reg_config(self, "embeddings_regularizer"))
+        if self.input_length is not None:
+            cfg["input_length"] = self.input_length
+        return cfg
+
+
 class Add(Layer):
     """Element-wise sum of same-shaped inputs (ResNet shortcut join)."""
     _prefix = "add"
@@ -1153,9 +1232,10 @@ class RandomZoom(_RandomAffine):
 
 
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
-                                         GlobalAveragePooling2D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
+                                         GlobalAveragePooling2D, GlobalAveragePooling1D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, GroupNormalization,
-                                         LayerNormalization, MultiHeadAttention, LSTM, GRU, Add, RandomFlip,
+                                         LayerNormalization, MultiHeadAttention, LSTM, GRU, Embedding, Add,
+                                         RandomFlip,
                                          RandomTranslation, RandomRotation, RandomZoom]}
 
 

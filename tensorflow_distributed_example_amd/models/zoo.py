@@ -174,6 +174,25 @@ def mnist_gru(name=None):
     ], name=name)
 
 
+def text_gap(vocab=2000, seq_len=32, dim=32, classes=4, name=None):
+    """The Keras text-classification starter: token ids [seq_len] -> Embedding -> mean over the steps -> Dense
+    (float32 layer-wise plan; csrc/kernels/embedding.hip)."""
+    return Sequential([
+        L.Embedding(vocab, dim, input_length=seq_len),
+        L.GlobalAveragePooling1D(),
+        L.Dense(classes),
+    ], name=name)
+
+
+def text_gru(vocab=2000, seq_len=32, dim=32, classes=4, name=None):
+    """Token ids -> Embedding -> GRU(64) -> Dense: the recurrent twin of ``text_gap``."""
+    return Sequential([
+        L.Embedding(vocab, dim, input_length=seq_len),
+        L.GRU(64),
+        L.Dense(classes),
+    ], name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

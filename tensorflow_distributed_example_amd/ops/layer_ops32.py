@@ -52,6 +52,9 @@ N.register_hip({
     # csrc/kernels/gru.hip
     "tde_gru32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),   # x, U, rb, hseq, hprev, acts, hlast, B, T, u
     "tde_gru32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),    # acts, hprev, U, dh, dx, dr, B, T, u, last_only
+    # csrc/kernels/embedding.hip
+    "tde_embed32_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),   # ids, table, out, n, V, D, ids_are_int
+    "tde_embed32_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),   # ids, dy, dtable, n, V, D, ids_are_int
 })
 
 _NODROP = DropSpec()
@@ -437,6 +440,47 @@ def gru_bwd(acts, hprev, rk, dh, dx, dr, B, T, units, last_only):
         _f32(t, k, f"gru_bwd {what}")
     N.check(N.hip().tde_gru32_bwd(_P(acts), _P(hprev), _P(rk), _P(dh), _P(dx), _P(dr), B, T, units,
                                   int(bool(last_only)), _s()), "tde_gru32_bwd")
+
+
+# ---------------------------------------------------------------- Embedding (csrc/kernels/embedding.hip)
+EMBED_MAX_V, EMBED_MAX_D = 2 ** 24, 512
+
+
+def embed_check(n, V, D, what):
+    """The supported range of csrc/kernels/embedding.hip: n tokens, a [V, D] table.  Ids travel as float32 (exact up
+    to 2^24) and every tensor is indexed by 32-bit element offsets."""
+    _req(n >= 1, f"{what}: empty geometry n={n}")
+    _req(1 <= V <= EMBED_MAX_V, f"{what}: input_dim={V} (from 1 to 2^24: ids are read as float32)")
+    _req(4 <= D <= EMBED_MAX_D and D % 4 == 0, f"{what}: output_dim={D} (a multiple of 4 from 4 to {EMBED_MAX_D})")
+    _req(n * D < 2 ** 31, f"{what}: n={n} x output_dim={D} (the output is addressed by 32-bit offsets: below 2^31)")
+    _req(V * D < 2 ** 31, f"{what}: input_dim={V} x output_dim={D} (the table is addressed by 32-bit offsets: below "
+                          "2^31)")
+
+
+def _embed_ids(ids, n, what):
+    _req(ids is not None and ids.dtype in (torch.float32, torch.int32) and ids.is_contiguous() and ids.numel() >= n,
+         f"{what}: f32 or i32 [{n}] expected")
+    return int(ids.dtype == torch.int32)
+
+
+def embed_fwd(ids, table, out, n, V, D):
+    """out [n, D] = table[ids]: ids float32 (truncated toward zero) or int32; an id outside [0, V) gives a zero
+    row."""
+    embed_check(n, V, D, "embed_fwd")
+    flag = _embed_ids(ids, n, "embed_fwd ids")
+    _f32(table, V * D, "embed_fwd table")
+    _f32(out, n * D, "embed_fwd out")
+    N.check(N.hip().tde_embed32_fwd(_P(ids), _P(table), _P(out), n, V, D, flag, _s()), "tde_embed32_fwd")
+
+
+def embed_bwd(ids, dy, dtable, n, V, D):
+    """dtable [V, D], written whole: row v is the float32 sum of the dy [n, D] rows whose id is v, added in token
+    order from zero (numpy's ``add.at`` bit for bit); ids outside [0, V) take no part.  One launch, no atomics."""
+    embed_check(n, V, D, "embed_bwd")
+    flag = _embed_ids(ids, n, "embed_bwd ids")
+    _f32(dy, n * D, "embed_bwd dy")
+    _f32(dtable, V * D, "embed_bwd dtable")
+    N.check(N.hip().tde_embed32_bwd(_P(ids), _P(dy), _P(dtable), n, V, D, flag, _s()), "tde_embed32_bwd")
 
 
 # ---------------------------------------------------------------- BatchNormalization / activations

@@ -286,6 +286,17 @@ class LayerwisePlan(PG.ReplicaPlan):
                                     names=("gru_cell/kernel", "gru_cell/bias"), bias_row=0))
                 stages.append(_Gru(self, layer, z, tout))
                 continue
+            if isinstance(layer, L.Embedding):
+                # the ids are the model input, read from the bound input buffer (csrc/kernels/embedding.hip)
+                who = f"{layer.name} (Embedding)"
+                if not self.f32:
+                    raise Unsupported(f"{who}: the gather and scatter-sum kernels are float32 only; the "
+                                      "mixed_bfloat16 policy has none")
+                if tin[0].root().id != 0:
+                    raise Unsupported(f"{who}: only the model input can feed an Embedding; ids produced by "
+                                      f"{nodes[tin[0].root().producer][0].name} have no gradient")
+                stages.append(_Embedding(self, layer, tin[0], tout))
+                continue
             if isinstance(layer, (L.BatchNormalization, L.Activation, L.Dropout, L.Add)):
                 if isinstance(layer, L.Activation) and layer.activation != "relu":
                     raise Unsupported(f"{layer.name}: activation {layer.activation!r} inside the network")
@@ -324,7 +335,7 @@ class LayerwisePlan(PG.ReplicaPlan):
             if isinstance(layer, L.MaxPooling2D):
                 stages.append(_MaxPool(self, layer, tin[0], tout))
                 continue
-            if isinstance(layer, L.GlobalAveragePooling2D):
+            if isinstance(layer, (L.GlobalAveragePooling2D, L.GlobalAveragePooling1D)):
                 stages.append(_GAP(self, layer, tin[0], tout))
                 continue
             if isinstance(layer, L.ZeroPadding2D):
@@ -1205,12 +1216,49 @@ class _Gru(_Stage):
             O32.act_bwd(self.dr, None, B * self.T, 3 * self.units, relu=False, dbias=self.grb)
 
 
+class _Embedding(_Stage):
+    """An Embedding on csrc/kernels/embedding.hip — float32 forms only.  The ids are the model input itself: the
+    forward reads the bound input buffer (the ring slot, float32 ids truncated by the kernel), so it has no
+    gradient input; the backward writes the whole gradient of ``embeddings``, zeros included, in one launch and in
+    token order (no atomics: bitwise reproducible).  Geometry: (B * T tokens, input_dim, output_dim)."""
+
+    def __init__(self, plan, layer, tin, tout):
+        self.layer, self.inp, self.out = layer, tin, tout
+        self.node_index = tout.producer
+        self.T, self.V, self.D = tin.numel, layer.input_dim, layer.output_dim
+        try:
+            O32.embed_check(*self.geom(plan.B), f"{layer.name} (Embedding)")
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        self.wname = f"{layer.name}/embeddings"
+        self.W = plan.store.view(self.wname)
+        self.gW = plan.store.grad(self.wname)
+
+    def geom(self, B):
+        return (B * self.T, self.V, self.D)
+
+    def param_names(self):
+        return [self.wname]
+
+    def alloc(self, B, dev):
+        pass
+
+    def grad_inputs(self):
+        return []
+
+    def fwd(self, p, B, training, mode="train"):
+        O32.embed_fwd(self.inp.root().buf, self.W, self.out.root().buf, *self.geom(B))
+
+    def bwd(self, p, B):
+        O32.embed_bwd(self.inp.root().buf, self.out.root().grad, self.gW, *self.geom(B))
+
+
 class _GAP(_Stage):
     def __init__(self, plan, layer, tin, tout):
         self.inp, self.out = tin, tout
         self.node_index = tout.producer
-        self.HW = tin.shape[0] * tin.shape[1]
-        self.C = tin.shape[2]
+        self.HW = int(np.prod(tin.shape[:-1]))   # [H, W, C], or the steps of a [T, C] sequence
+        self.C = tin.C
         self.O = O32 if plan.f32 else O
 
     def alloc(self, B, dev):
@@ -1537,7 +1585,10 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             o = F.max_pool2d(a, (g.KH, g.KW), (g.sh, g.sw)).permute(0, 2, 3, 1)
             vals[stg.out.root().id] = o.reshape(B, -1)
         elif isinstance(stg, _GAP):
-            vals[stg.out.root().id] = QR(get(stg.inp).mean((1, 2)).reshape(B, -1))
+            a = get(stg.inp)
+            vals[stg.out.root().id] = QR(a.mean(tuple(range(1, a.dim() - 1))).reshape(B, -1))
+        elif isinstance(stg, _Embedding):
+            vals[stg.out.root().id] = L.Embedding.lookup(get(stg.inp), W[stg.wname]).reshape(B, -1)
         elif isinstance(stg, _Pad):
             g = stg.geo
             a = get(stg.inp)
