@@ -35,6 +35,11 @@
 //   apart: both spread over all 64 banks without an XOR (3u / 4 columns are no power of two) and without a
 //   fourth slot per unit.  Four independent accumulator chains over the 3u / 4 k-steps, added in one written
 //   order; one writer per element, no atomics: bitwise reproducible.
+// * Bidirectional (the BI instantiations, grid (ceil(N / 16), 2)): as in lstm.hip.  blockIdx.y is the direction and
+//   picks its operand set; direction 1's forward sweep walks t = T-1 .. 0 and its backward sweep t = 0 .. T-1;
+//   "first", "last", "next" and the LDS parity count steps, not t; hprev of direction 1 at position t is h of
+//   position t + 1; h goes straight into columns d u .. of the [N, T, 2u] (or [N, 2u]) output and dh is read from
+//   there.  The unidirectional instantiations are BI = false: one direction, step = t, every stride a constant u.
 #include "tde_common.h"
 
 #include <cstdint>
@@ -46,17 +51,27 @@ constexpr int kRows = 16;              // batch rows per workgroup
 constexpr int kMinU = 16, kMaxU = 128;
 constexpr float kLog2e = 1.4426950408889634f;
 
-struct FwdArgs {
+// One direction's operands.  BI: hseq, hlast and dh point at the direction's column d u of a row that is 2u wide
+// (hseq: hld wide, u for a dense tensor of its own) and hseq may be null.
+struct FwdDir {
   const float* x; const float* u;
   const float* rb;   // [3u] or null
   float* hseq; float* hprev; float* acts;
   float* hlast;      // [N, u] or null
-  int N, T;
 };
-struct BwdArgs {
+template <bool BI>
+struct FwdArgs {
+  FwdDir d[BI ? 2 : 1];
+  int N, T, hld;
+};
+struct BwdDir {
   const float* acts; const float* hprev; const float* u;
   const float* dh;   // [N, T, u], or [N, u] with last_only
   float* dx; float* dr;
+};
+template <bool BI>
+struct BwdArgs {
+  BwdDir d[BI ? 2 : 1];
   int N, T, last_only;
 };
 
@@ -107,13 +122,17 @@ __device__ __forceinline__ f32x4 load_rows(const float* base, const Rows& x) {
 }
 
 // ---------------------------------------------------------------------------------------------- forward
-template <int NCH>   // u / 16: waves per workgroup and 16-float chunks of K
-__global__ __launch_bounds__(64 * NCH) void gru_fwd_kernel(const FwdArgs p) {
-  constexpr int U = 16 * NCH, LD = U + 4, W3 = 3 * U, W4 = 4 * U;
+template <int NCH, bool BI>   // NCH = u / 16: waves per workgroup and 16-float chunks of K
+__global__ __launch_bounds__(64 * NCH) void gru_fwd_kernel(const FwdArgs<BI> p) {
+  constexpr int U = 16 * NCH, LD = U + 4, W3 = 3 * U, W4 = 4 * U, HL = BI ? 2 * U : U;
   __shared__ __attribute__((aligned(16))) float himg[2][kRows * LD];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
   const int col = 16 * w + fr, N = p.N, T = p.T;
+  const bool rev = BI && blockIdx.y;   // direction 1 walks t = T-1 .. 0
+  const FwdDir q = rev ? p.d[BI] : p.d[0];
+  const int dt = rev ? -1 : 1, hld = BI ? p.hld : U;
   const Rows x3 = rows_of(fq, N, T, W3, col), x4 = rows_of(fq, N, T, W4, col), x1 = rows_of(fq, N, T, U, col);
+  const Rows xh = rows_of(fq, N, T, hld, col);
 
   float ub[NCH][4][3];   // [chunk][k = 16 ch + 4 fq + j][gate]: B[k][n = fr]
 #pragma unroll
@@ -121,34 +140,35 @@ __global__ __launch_bounds__(64 * NCH) void gru_fwd_kernel(const FwdArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int g = 0; g < 3; ++g) ub[ch][j][g] = p.u[(16 * ch + 4 * fq + j) * W3 + g * U + col];
+      for (int g = 0; g < 3; ++g) ub[ch][j][g] = q.u[(16 * ch + 4 * fq + j) * W3 + g * U + col];
   float rb[3];           // the recurrent bias of the lane's unit, gate by gate
 #pragma unroll
-  for (int g = 0; g < 3; ++g) rb[g] = p.rb ? p.rb[g * U + col] : 0.f;
+  for (int g = 0; g < 3; ++g) rb[g] = q.rb ? q.rb[g * U + col] : 0.f;
 
   f32x4 xn[3];   // X of the coming step, gate by gate
 #pragma unroll
-  for (int g = 0; g < 3; ++g) xn[g] = load_rows(at(p.x, T, W3, 0) + g * U, x3);
+  for (int g = 0; g < 3; ++g) xn[g] = load_rows(at(q.x, T, W3, rev ? T - 1 : 0) + g * U, x3);
   f32x4 h = {0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll 1
-  for (int t = 0; t < T; ++t) {
+  for (int s = 0, t = rev ? T - 1 : 0; s < T; ++s, t += dt) {   // step s works on position t
+    const bool more = s + 1 < T;
     // z and r: X + rb + h U as one sum.  The candidate: rb_h + h U_h alone, X_h joins after the reset gate
     f32x4 acc[3] = {xn[0] + rb[0], xn[1] + rb[1], f32x4{rb[2], rb[2], rb[2], rb[2]}};
     f32x4 act = xn[2];   // X_h now, hh after the gate math
-    if (t + 1 < T) {
-      const float* xt = at(p.x, T, W3, t + 1);
+    if (more) {
+      const float* xt = at(q.x, T, W3, t + dt);
 #pragma unroll
       for (int g = 0; g < 3; ++g) xn[g] = load_rows(xt + g * U, x3);
     }
-    {   // hprev of this step: h_{t-1}, zeros at t = 0
-      float* hp = at(p.hprev, T, U, t);
+    {   // hprev of this step: h of the step before, zeros at s = 0
+      float* hp = at(q.hprev, T, U, t);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (x1.ok[r]) elem(hp, x1.off[r]) = h[r];
     }
-    if (t > 0) {   // h_{-1} = 0
-      const float* hb = himg[t & 1] + fr * LD + 4 * fq;
+    if (s > 0) {   // from a zero state
+      const float* hb = himg[s & 1] + fr * LD + 4 * fq;
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(hb + 16 * ch);
@@ -165,13 +185,14 @@ __global__ __launch_bounds__(64 * NCH) void gru_fwd_kernel(const FwdArgs p) {
       h[r] = zg * h[r] + (1.f - zg) * hh;
       acc[0][r] = zg; acc[1][r] = rg; act[r] = hh;   // acc[2] stays R_h
     }
-    if (t + 1 < T) {
-      float* hw = himg[(t + 1) & 1] + 4 * fq * LD + col;
+    if (more) {
+      float* hw = himg[(s + 1) & 1] + 4 * fq * LD + col;
 #pragma unroll
       for (int r = 0; r < 4; ++r) hw[r * LD] = h[r];
     }
-    float* at_ = at(p.acts, T, W4, t);
-    float* ht = at(p.hseq, T, U, t);
+    float* at_ = at(q.acts, T, W4, t);
+    float* ht = at(q.hseq, T, hld, t);
+    const bool hs = !BI || q.hseq;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (x1.ok[r]) {
@@ -179,26 +200,31 @@ __global__ __launch_bounds__(64 * NCH) void gru_fwd_kernel(const FwdArgs p) {
         elem(at_ + U, x4.off[r]) = acc[1][r];
         elem(at_ + 2 * U, x4.off[r]) = act[r];
         elem(at_ + 3 * U, x4.off[r]) = acc[2][r];
-        elem(ht, x1.off[r]) = h[r];
+        if (hs) elem(ht, xh.off[r]) = h[r];
       }
-    if (t + 1 < T) lds_barrier();
+    if (more) lds_barrier();
   }
-  if (p.hlast) {
+  if (q.hlast) {
     const int first = blockIdx.x * kRows + 4 * fq;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (x1.ok[r]) p.hlast[(size_t)(first + r) * U + col] = h[r];
+      if (x1.ok[r]) q.hlast[(size_t)(first + r) * HL + col] = h[r];
   }
 }
 
 // ---------------------------------------------------------------------------------------------- backward
-template <int NCH>
-__global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
+template <int NCH, bool BI>
+__global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs<BI> p) {
   constexpr int U = 16 * NCH, K = 3 * U, LD = K + 4, W4 = 4 * U, NK = 3 * NCH;   // NK 16-float chunks of K
+  constexpr int DH = BI ? 2 * U : U;                                             // the row of the upstream dh
   __shared__ __attribute__((aligned(16))) float dimg[2][kRows * LD];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
   const int col = 16 * w + fr, N = p.N, T = p.T;
+  const bool up_ = BI && blockIdx.y;   // direction 1's backward walks t = 0 .. T-1
+  const BwdDir q = up_ ? p.d[BI] : p.d[0];
+  const int dt = up_ ? 1 : -1, t0 = up_ ? 0 : T - 1;
   const Rows x3 = rows_of(fq, N, T, K, col), x4 = rows_of(fq, N, T, W4, col), x1 = rows_of(fq, N, T, U, col);
+  const Rows xd = rows_of(fq, N, T, DH, col);
 
   // the image's K order is U's column order (k = gate u + unit); lane group fq reads k = 16 ch + 4 fq + j for the
   // j-th MFMA of chunk ch
@@ -206,31 +232,33 @@ __global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
 #pragma unroll
   for (int ch = 0; ch < NK; ++ch)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ub[ch][j] = p.u[col * K + 16 * ch + 4 * fq + j];
+    for (int j = 0; j < 4; ++j) ub[ch][j] = q.u[col * K + 16 * ch + 4 * fq + j];
 
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const int seq = !p.last_only;
-  // the operands of the coming step: z, r, hh, R_h, then h_{t-1} and the upstream dh_t
+  // the operands of the coming step: z, r, hh, R_h, then hprev and the upstream dh_t
   f32x4 an[4], hpn, upn;
 #pragma unroll
-  for (int g = 0; g < 4; ++g) an[g] = load_rows(at(p.acts, T, W4, T - 1) + g * U, x4);
-  hpn = load_rows(at(p.hprev, T, U, T - 1), x1);
+  for (int g = 0; g < 4; ++g) an[g] = load_rows(at(q.acts, T, W4, t0) + g * U, x4);
+  hpn = load_rows(at(q.hprev, T, U, t0), x1);
   if (seq) {
-    upn = load_rows(at(p.dh, T, U, T - 1), x1);
-  } else {   // [N, u]: the rows_of of a one-step tensor
-    upn = load_rows(at(p.dh, 1, U, 0), rows_of(fq, N, 1, U, col));
+    upn = load_rows(at(q.dh, T, DH, t0), xd);
+  } else {   // [N, DH]: the rows_of of a one-step tensor
+    upn = load_rows(at(q.dh, 1, DH, 0), rows_of(fq, N, 1, DH, col));
   }
   f32x4 dhr = zero;
 
 #pragma unroll 1
-  for (int t = T - 1; t >= 0; --t) {
+  for (int s = T - 1; s >= 0; --s) {   // s steps remain after this one, which works on position t
+    const int t = up_ ? T - 1 - s : s;
+    const bool more = s > 0;
     const f32x4 zg = an[0], rg = an[1], hh = an[2], rh = an[3], hp = hpn, up = upn;
-    if (t > 0) {
-      const float* a1 = at(p.acts, T, W4, t - 1);
+    if (more) {
+      const float* a1 = at(q.acts, T, W4, t + dt);
 #pragma unroll
       for (int g = 0; g < 4; ++g) an[g] = load_rows(a1 + g * U, x4);
-      hpn = load_rows(at(p.hprev, T, U, t - 1), x1);
-      upn = seq ? load_rows(at(p.dh, T, U, t - 1), x1) : zero;
+      hpn = load_rows(at(q.hprev, T, U, t + dt), x1);
+      upn = seq ? load_rows(at(q.dh, T, DH, t + dt), xd) : zero;
     }
     f32x4 dxz, dxr, da, drh, keep;   // keep: dh z, the lane-local half of the next dhr
 #pragma unroll
@@ -242,8 +270,8 @@ __global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
       drh[r] = da[r] * rg[r];
       keep[r] = dh * zg[r];
     }
-    float* img = dimg[t & 1];
-    if (t > 0) {
+    float* img = dimg[s & 1];
+    if (more) {
       float* iw = img + 4 * fq * LD + col;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -252,8 +280,8 @@ __global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
         iw[r * LD + 2 * U] = drh[r];
       }
     }
-    float* dxt = at(p.dx, T, K, t);
-    float* drt = at(p.dr, T, K, t);
+    float* dxt = at(q.dx, T, K, t);
+    float* drt = at(q.dr, T, K, t);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (x1.ok[r]) {
@@ -264,7 +292,7 @@ __global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
         elem(drt + U, x3.off[r]) = dxr[r];
         elem(drt + 2 * U, x3.off[r]) = drh[r];
       }
-    if (t == 0) break;
+    if (!more) break;
     lds_barrier();
     f32x4 acc[4] = {zero, zero, zero, zero};   // four independent chains, summed in a fixed order
     const float* ir = img + fr * LD + 4 * fq;
@@ -278,9 +306,11 @@ __global__ __launch_bounds__(64 * NCH) void gru_bwd_kernel(const BwdArgs p) {
   }
 }
 
-static bool geo_ok(int N, int T, int units) {
+// hrow: the widest row that holds h or dh (u, or 2u for the bidirectional output); the activations' row is 4u
+static bool geo_ok(int N, int T, int units, int hrow) {
   if (N < 1 || T < 1 || units < kMinU || units > kMaxU || units % 16) return false;
-  return (long long)kRows * T * 4 * units * 4 < (1LL << 32);   // a workgroup's rows by 32-bit byte offsets
+  const int row = hrow > 4 * units ? hrow : 4 * units;
+  return (long long)kRows * T * row * 4 < (1LL << 32);   // a workgroup's rows by 32-bit byte offsets
 }
 
 }  // namespace gru
@@ -300,32 +330,74 @@ using namespace tde::gru;
     default: LAUNCH(8); break;   \
   }
 
+template <bool BI>
+static void launch_fwd(const FwdArgs<BI>& a, int units, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.N + kRows - 1) / kRows), BI ? 2 : 1);
+#define TDE_GRU_FWD(n) gru_fwd_kernel<n, BI><<<grid, 64 * n, 0, stream>>>(a)
+  TDE_GRU_DISPATCH(TDE_GRU_FWD)
+#undef TDE_GRU_FWD
+}
+
+// the image is static LDS: 384 units + 512 bytes
+template <bool BI>
+static void launch_bwd(const BwdArgs<BI>& a, int units, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.N + kRows - 1) / kRows), BI ? 2 : 1);
+#define TDE_GRU_BWD(n) gru_bwd_kernel<n, BI><<<grid, 64 * n, 0, stream>>>(a)
+  TDE_GRU_DISPATCH(TDE_GRU_BWD)
+#undef TDE_GRU_BWD
+}
+
 // hseq, hprev, acts (and hlast [N, units] unless null) from X = x W + b[0] [N, T, 3 units], U [units, 3 units] and the
 // recurrent bias rb [3 units] (null: none)
 TDE_API int tde_gru32_fwd(const float* x, const float* u, const float* rb, float* hseq, float* hprev, float* acts,
                           float* hlast, int N, int T, int units, hipStream_t stream) {
-  if (!geo_ok(N, T, units)) return -1;
+  if (!geo_ok(N, T, units, units)) return -1;
   if (!x || !u || !hseq || !hprev || !acts) return -2;
-  const FwdArgs a = {x, u, rb, hseq, hprev, acts, hlast, N, T};
-  const dim3 grid((unsigned)((N + kRows - 1) / kRows));
-#define TDE_GRU_FWD(n) gru_fwd_kernel<n><<<grid, 64 * n, 0, stream>>>(a)
-  TDE_GRU_DISPATCH(TDE_GRU_FWD)
-#undef TDE_GRU_FWD
+  const FwdArgs<false> a = {{{x, u, rb, hseq, hprev, acts, hlast}}, N, T, units};
+  launch_fwd(a, units, stream);
   TDE_LAUNCH_CHECK();
   return 0;
 }
 
 // dX and dR [N, T, 3 units] from the forward's activations and h_{t-1} and the upstream dh ([N, T, units], or
-// [N, units] for the last step only with last_only).  The image is static LDS: 384 units + 512 bytes.
+// [N, units] for the last step only with last_only)
 TDE_API int tde_gru32_bwd(const float* acts, const float* hprev, const float* u, const float* dh, float* dx, float* dr,
                           int N, int T, int units, int last_only, hipStream_t stream) {
-  if (!geo_ok(N, T, units)) return -1;
+  if (!geo_ok(N, T, units, units)) return -1;
   if (!acts || !hprev || !u || !dh || !dx || !dr) return -2;
-  const BwdArgs a = {acts, hprev, u, dh, dx, dr, N, T, last_only};
-  const dim3 grid((unsigned)((N + kRows - 1) / kRows));
-#define TDE_GRU_BWD(n) gru_bwd_kernel<n><<<grid, 64 * n, 0, stream>>>(a)
-  TDE_GRU_DISPATCH(TDE_GRU_BWD)
-#undef TDE_GRU_BWD
+  const BwdArgs<false> a = {{{acts, hprev, u, dh, dx, dr}}, N, T, last_only};
+  launch_bwd(a, units, stream);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// Both directions of a bidirectional layer in one launch.  Direction d (0: forward in time, 1: backward in time)
+// has its own X_d, U_d, rb_d (null: none) and saved tensors hprev_d, acts_d.  seq: every h into out [N, T, 2 units],
+// columns d units .. of position t in the original time order (hseq_d unused).  Otherwise: the directions' final
+// states into out [N, 2 units], and every h into hseq_d [N, T, units] unless null.
+TDE_API int tde_gru32_bi_fwd(const float* x0, const float* x1, const float* u0, const float* u1, const float* rb0,
+                             const float* rb1, float* hseq0, float* hseq1, float* hprev0, float* hprev1, float* acts0,
+                             float* acts1, float* out, int N, int T, int units, int seq, hipStream_t stream) {
+  if (!geo_ok(N, T, units, 2 * units)) return -1;
+  if (!x0 || !x1 || !u0 || !u1 || !hprev0 || !hprev1 || !acts0 || !acts1 || !out) return -2;
+  const FwdArgs<true> a = {{{x0, u0, rb0, seq ? out : hseq0, hprev0, acts0, seq ? nullptr : out},
+                            {x1, u1, rb1, seq ? out + units : hseq1, hprev1, acts1, seq ? nullptr : out + units}},
+                           N, T, seq ? 2 * units : units};
+  launch_fwd(a, units, stream);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// dX_d and dR_d [N, T, 3 units] of both directions from the upstream dh [N, T, 2 units] (or [N, 2 units] with
+// last_only: the gradient of the final states), direction d reading columns d units ..
+TDE_API int tde_gru32_bi_bwd(const float* acts0, const float* acts1, const float* hprev0, const float* hprev1,
+                             const float* u0, const float* u1, const float* dh, float* dx0, float* dx1, float* dr0,
+                             float* dr1, int N, int T, int units, int last_only, hipStream_t stream) {
+  if (!geo_ok(N, T, units, 2 * units)) return -1;
+  if (!acts0 || !acts1 || !hprev0 || !hprev1 || !u0 || !u1 || !dh || !dx0 || !dx1 || !dr0 || !dr1) return -2;
+  const BwdArgs<true> a = {{{acts0, hprev0, u0, dh, dx0, dr0}, {acts1, hprev1, u1, dh + units, dx1, dr1}},
+                           N, T, last_only};
+  launch_bwd(a, units, stream);
   TDE_LAUNCH_CHECK();
   return 0;
 }

@@ -31,6 +31,15 @@
 //   The gate activations, c_{t-1} and the upstream dh_t of step t - 1 are loaded while step t computes.
 //   One writer per element, no atomics: bitwise reproducible.
 // * sigmoid and tanh run on v_exp_f32 / v_rcp_f32 with log2(e) folded into the argument.
+// * Bidirectional (the BI instantiations, grid (ceil(N / 16), 2)): blockIdx.y is the direction and picks its
+//   operand set; a direction's workgroups are the ones above.  Time order belongs to the direction: in the forward
+//   sweep direction 0 walks t = 0 .. T-1 and direction 1 walks t = T-1 .. 0, in the backward sweep each walks the
+//   other way, and everything that says "first", "last" or "next" (the prefetches, the zero state, the LDS parity)
+//   counts STEPS s (up from 0 in the forward sweep, down to 0 in the backward sweep), not t.  hprev of direction 1 at position t is therefore h of position t + 1, zeros
+//   at T-1.  h goes straight into the direction's half of the layer's output ([N, T, 2u], row stride 2u, column
+//   offset d u, original time order; or the final states into [N, 2u]) and the upstream dh is read from the same
+//   halves: no reverse, concat or split exists.  The unidirectional instantiations are BI = false: one direction,
+//   s = t, every stride a compile-time u.
 #include "tde_common.h"
 
 #include <cstdint>
@@ -42,16 +51,26 @@ constexpr int kRows = 16;              // batch rows per workgroup
 constexpr int kMinU = 16, kMaxU = 128;
 constexpr float kLog2e = 1.4426950408889634f;
 
-struct FwdArgs {
+// One direction's operands.  BI: hseq, hlast and dh point at the direction's column d u of a row that is 2u wide
+// (hseq: hld wide, u for a dense tensor of its own) and hseq may be null.
+struct FwdDir {
   const float* z; const float* u;
   float* hseq; float* hprev; float* gates; float* cseq;
   float* hlast;     // [N, u] or null
-  int N, T;
 };
-struct BwdArgs {
+template <bool BI>
+struct FwdArgs {
+  FwdDir d[BI ? 2 : 1];
+  int N, T, hld;
+};
+struct BwdDir {
   const float* gates; const float* cseq; const float* u;
   const float* dh;  // [N, T, u], or [N, u] with last_only
   float* dz;
+};
+template <bool BI>
+struct BwdArgs {
+  BwdDir d[BI ? 2 : 1];
   int N, T, last_only;
 };
 
@@ -103,13 +122,16 @@ __device__ __forceinline__ f32x4 load_rows(const float* base, const Rows& x) {
 }
 
 // ---------------------------------------------------------------------------------------------- forward
-template <int NCH>   // u / 16: waves per workgroup and 16-float chunks of K
-__global__ __launch_bounds__(64 * NCH) void lstm_fwd_kernel(const FwdArgs p) {
-  constexpr int U = 16 * NCH, LD = U + 4, W4 = 4 * U;
+template <int NCH, bool BI>   // NCH = u / 16: waves per workgroup and 16-float chunks of K
+__global__ __launch_bounds__(64 * NCH) void lstm_fwd_kernel(const FwdArgs<BI> p) {
+  constexpr int U = 16 * NCH, LD = U + 4, W4 = 4 * U, HL = BI ? 2 * U : U;
   __shared__ __attribute__((aligned(16))) float himg[2][kRows * LD];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
   const int col = 16 * w + fr, N = p.N, T = p.T;
-  const Rows x4 = rows_of(fq, N, T, W4, col), x1 = rows_of(fq, N, T, U, col);
+  const bool rev = BI && blockIdx.y;   // direction 1 walks t = T-1 .. 0
+  const FwdDir q = rev ? p.d[BI] : p.d[0];
+  const int dt = rev ? -1 : 1, hld = BI ? p.hld : U;
+  const Rows x4 = rows_of(fq, N, T, W4, col), x1 = rows_of(fq, N, T, U, col), xh = rows_of(fq, N, T, hld, col);
 
   float ub[NCH][4][4];   // [chunk][k = 16 ch + 4 fq + j][gate]: B[k][n = fr]
 #pragma unroll
@@ -117,31 +139,32 @@ __global__ __launch_bounds__(64 * NCH) void lstm_fwd_kernel(const FwdArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) ub[ch][j][g] = p.u[(16 * ch + 4 * fq + j) * W4 + g * U + col];
+      for (int g = 0; g < 4; ++g) ub[ch][j][g] = q.u[(16 * ch + 4 * fq + j) * W4 + g * U + col];
 
   f32x4 zn[4];   // Z of the coming step, gate by gate
 #pragma unroll
-  for (int g = 0; g < 4; ++g) zn[g] = load_rows(at(p.z, T, W4, 0) + g * U, x4);
+  for (int g = 0; g < 4; ++g) zn[g] = load_rows(at(q.z, T, W4, rev ? T - 1 : 0) + g * U, x4);
   f32x4 c = {0.f, 0.f, 0.f, 0.f}, h = c;
 
 #pragma unroll 1
-  for (int t = 0; t < T; ++t) {
+  for (int s = 0, t = rev ? T - 1 : 0; s < T; ++s, t += dt) {   // step s works on position t
+    const bool more = s + 1 < T;
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[g] = zn[g];
-    if (t + 1 < T) {
-      const float* zt = at(p.z, T, W4, t + 1);
+    if (more) {
+      const float* zt = at(q.z, T, W4, t + dt);
 #pragma unroll
       for (int g = 0; g < 4; ++g) zn[g] = load_rows(zt + g * U, x4);
     }
-    {   // hprev of this step: h_{t-1}, zeros at t = 0
-      float* hp = at(p.hprev, T, U, t);
+    {   // hprev of this step: h of the step before, zeros at s = 0
+      float* hp = at(q.hprev, T, U, t);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (x1.ok[r]) elem(hp, x1.off[r]) = h[r];
     }
-    if (t > 0) {   // h_{-1} = 0
-      const float* hb = himg[t & 1] + fr * LD + 4 * fq;
+    if (s > 0) {   // from a zero state
+      const float* hb = himg[s & 1] + fr * LD + 4 * fq;
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(hb + 16 * ch);
@@ -158,29 +181,30 @@ __global__ __launch_bounds__(64 * NCH) void lstm_fwd_kernel(const FwdArgs p) {
       h[r] = og * tanh_(c[r]);
       acc[0][r] = ig; acc[1][r] = fg; acc[2][r] = gg; acc[3][r] = og;
     }
-    if (t + 1 < T) {
-      float* hw = himg[(t + 1) & 1] + 4 * fq * LD + col;
+    if (more) {
+      float* hw = himg[(s + 1) & 1] + 4 * fq * LD + col;
 #pragma unroll
       for (int r = 0; r < 4; ++r) hw[r * LD] = h[r];
     }
-    float* gt = at(p.gates, T, W4, t);
-    float* ct = at(p.cseq, T, U, t);
-    float* ht = at(p.hseq, T, U, t);
+    float* gt = at(q.gates, T, W4, t);
+    float* ct = at(q.cseq, T, U, t);
+    float* ht = at(q.hseq, T, hld, t);
+    const bool hs = !BI || q.hseq;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (x1.ok[r]) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) elem(gt + g * U, x4.off[r]) = acc[g][r];
         elem(ct, x1.off[r]) = c[r];
-        elem(ht, x1.off[r]) = h[r];
+        if (hs) elem(ht, xh.off[r]) = h[r];
       }
-    if (t + 1 < T) lds_barrier();
+    if (more) lds_barrier();
   }
-  if (p.hlast) {
+  if (q.hlast) {
     const int first = blockIdx.x * kRows + 4 * fq;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (x1.ok[r]) p.hlast[(size_t)(first + r) * U + col] = h[r];
+      if (x1.ok[r]) q.hlast[(size_t)(first + r) * HL + col] = h[r];
   }
 }
 
@@ -188,13 +212,16 @@ __global__ __launch_bounds__(64 * NCH) void lstm_fwd_kernel(const FwdArgs p) {
 // float offset of (row, 16-byte column c4) in a swizzled [16][K] image
 __device__ __forceinline__ int swz(int row, int c4, int K) { return row * K + ((c4 ^ row) << 2); }
 
-template <int NCH>
-__global__ __launch_bounds__(64 * NCH) void lstm_bwd_kernel(const BwdArgs p) {
-  constexpr int U = 16 * NCH, K = 4 * U;
+template <int NCH, bool BI>
+__global__ __launch_bounds__(64 * NCH) void lstm_bwd_kernel(const BwdArgs<BI> p) {
+  constexpr int U = 16 * NCH, K = 4 * U, DH = BI ? 2 * U : U;   // DH: the row of the upstream dh
   extern __shared__ __attribute__((aligned(16))) float dimg[];   // [2][16][K]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
   const int col = 16 * w + fr, N = p.N, T = p.T;
-  const Rows x4 = rows_of(fq, N, T, K, col), x1 = rows_of(fq, N, T, U, col);
+  const bool up_ = BI && blockIdx.y;   // direction 1's backward walks t = 0 .. T-1
+  const BwdDir q = up_ ? p.d[BI] : p.d[0];
+  const int dt = up_ ? 1 : -1, t0 = up_ ? 0 : T - 1;
+  const Rows x4 = rows_of(fq, N, T, K, col), x1 = rows_of(fq, N, T, U, col), xd = rows_of(fq, N, T, DH, col);
 
   // the image's K order is unit-major, gate-minor (k = 4 unit + gate): a lane's di, df, dg, do of one (row, unit)
   // are one 16-byte write, and lane group fq reads unit 4 ch + fq of chunk ch, gate j for the j-th MFMA
@@ -202,35 +229,38 @@ __global__ __launch_bounds__(64 * NCH) void lstm_bwd_kernel(const BwdArgs p) {
 #pragma unroll
   for (int ch = 0; ch < 4 * NCH; ++ch)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ub[ch][j] = p.u[col * K + j * U + 4 * ch + fq];
+    for (int j = 0; j < 4; ++j) ub[ch][j] = q.u[col * K + j * U + 4 * ch + fq];
 
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const int seq = !p.last_only;
-  // the operands of the coming step: the four activations, c_{t-1} and the upstream dh_t
+  // the operands of the coming step: the four activations, the c of the position the forward came from (t + dt)
+  // and the upstream dh_t
   f32x4 gn[4], cpn = zero, upn;
 #pragma unroll
-  for (int g = 0; g < 4; ++g) gn[g] = load_rows(at(p.gates, T, K, T - 1) + g * U, x4);
-  if (T > 1) cpn = load_rows(at(p.cseq, T, U, T - 2), x1);
+  for (int g = 0; g < 4; ++g) gn[g] = load_rows(at(q.gates, T, K, t0) + g * U, x4);
+  if (T > 1) cpn = load_rows(at(q.cseq, T, U, t0 + dt), x1);
   if (seq) {
-    upn = load_rows(at(p.dh, T, U, T - 1), x1);
-  } else {   // [N, u]: the rows_of of a one-step tensor
-    upn = load_rows(at(p.dh, 1, U, 0), rows_of(fq, N, 1, U, col));
+    upn = load_rows(at(q.dh, T, DH, t0), xd);
+  } else {   // [N, DH]: the rows_of of a one-step tensor
+    upn = load_rows(at(q.dh, 1, DH, 0), rows_of(fq, N, 1, DH, col));
   }
-  f32x4 cc = load_rows(at(p.cseq, T, U, T - 1), x1);   // c_t
+  f32x4 cc = load_rows(at(q.cseq, T, U, t0), x1);   // c_t
   f32x4 dc = zero, dhr = zero;
 
 #pragma unroll 1
-  for (int t = T - 1; t >= 0; --t) {
+  for (int s = T - 1; s >= 0; --s) {   // s steps remain after this one, which works on position t
+    const int t = up_ ? T - 1 - s : s;
+    const bool more = s > 0;
     f32x4 ga[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) ga[g] = gn[g];
     const f32x4 cp = cpn, up = upn;
-    if (t > 0) {
-      const float* gt = at(p.gates, T, K, t - 1);
+    if (more) {
+      const float* gt = at(q.gates, T, K, t + dt);
 #pragma unroll
       for (int g = 0; g < 4; ++g) gn[g] = load_rows(gt + g * U, x4);
-      cpn = t > 1 ? load_rows(at(p.cseq, T, U, t - 2), x1) : zero;
-      upn = seq ? load_rows(at(p.dh, T, U, t - 1), x1) : zero;
+      cpn = s > 1 ? load_rows(at(q.cseq, T, U, t + 2 * dt), x1) : zero;
+      upn = seq ? load_rows(at(q.dh, T, DH, t + dt), xd) : zero;
     }
     f32x4 dzv[4];
 #pragma unroll
@@ -245,20 +275,20 @@ __global__ __launch_bounds__(64 * NCH) void lstm_bwd_kernel(const BwdArgs p) {
       dc[r] *= fg;
     }
     cc = cp;
-    float* img = dimg + (t & 1) * (kRows * K);
-    if (t > 0) {
+    float* img = dimg + (s & 1) * (kRows * K);
+    if (more) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         *reinterpret_cast<f32x4*>(img + swz(4 * fq + r, col, K)) = f32x4{dzv[0][r], dzv[1][r], dzv[2][r], dzv[3][r]};
     }
-    float* dzt = at(p.dz, T, K, t);
+    float* dzt = at(q.dz, T, K, t);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (x1.ok[r]) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) elem(dzt + g * U, x4.off[r]) = dzv[g][r];
       }
-    if (t == 0) break;
+    if (!more) break;
     lds_barrier();
     f32x4 acc[4] = {zero, zero, zero, zero};   // four independent chains, summed in a fixed order
 #pragma unroll
@@ -271,9 +301,11 @@ __global__ __launch_bounds__(64 * NCH) void lstm_bwd_kernel(const BwdArgs p) {
   }
 }
 
-static bool geo_ok(int N, int T, int units) {
+// hrow: the widest row that holds h or dh (u, or 2u for the bidirectional output); the gates' row is 4u
+static bool geo_ok(int N, int T, int units, int hrow) {
   if (N < 1 || T < 1 || units < kMinU || units > kMaxU || units % 16) return false;
-  return (long long)kRows * T * 4 * units * 4 < (1LL << 32);   // a workgroup's rows by 32-bit byte offsets
+  const int row = hrow > 4 * units ? hrow : 4 * units;
+  return (long long)kRows * T * row * 4 < (1LL << 32);   // a workgroup's rows by 32-bit byte offsets
 }
 
 }  // namespace lstm
@@ -293,16 +325,39 @@ using namespace tde::lstm;
     default: LAUNCH(8); break;    \
   }
 
+template <bool BI>
+static void launch_fwd(const FwdArgs<BI>& a, int units, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.N + kRows - 1) / kRows), BI ? 2 : 1);
+#define TDE_LSTM_FWD(n) lstm_fwd_kernel<n, BI><<<grid, 64 * n, 0, stream>>>(a)
+  TDE_LSTM_DISPATCH(TDE_LSTM_FWD)
+#undef TDE_LSTM_FWD
+}
+
+template <bool BI>
+static void launch_bwd(const BwdArgs<BI>& a, int units, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.N + kRows - 1) / kRows), BI ? 2 : 1);
+  const int lds = 2 * kRows * 4 * units * (int)sizeof(float);   // 64 KiB at the upper end
+  static bool attr_set = false;   // one per instantiation of this function
+  if (!attr_set) {
+#define TDE_LSTM_ATTR(n) \
+  (void)hipFuncSetAttribute((const void*)lstm_bwd_kernel<n, BI>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kRows * 64 * n * 4)
+    TDE_LSTM_ATTR(1); TDE_LSTM_ATTR(2); TDE_LSTM_ATTR(3); TDE_LSTM_ATTR(4);
+    TDE_LSTM_ATTR(5); TDE_LSTM_ATTR(6); TDE_LSTM_ATTR(7); TDE_LSTM_ATTR(8);
+#undef TDE_LSTM_ATTR
+    attr_set = true;
+  }
+#define TDE_LSTM_BWD(n) lstm_bwd_kernel<n, BI><<<grid, 64 * n, lds, stream>>>(a)
+  TDE_LSTM_DISPATCH(TDE_LSTM_BWD)
+#undef TDE_LSTM_BWD
+}
+
 // hseq, hprev, gates, cseq (and hlast [N, units] unless null) from Z = x W + b [N, T, 4 units] and U [units, 4 units]
 TDE_API int tde_lstm32_fwd(const float* z, const float* u, float* hseq, float* hprev, float* gates, float* cseq,
                            float* hlast, int N, int T, int units, hipStream_t stream) {
-  if (!geo_ok(N, T, units)) return -1;
+  if (!geo_ok(N, T, units, units)) return -1;
   if (!z || !u || !hseq || !hprev || !gates || !cseq) return -2;
-  const FwdArgs a = {z, u, hseq, hprev, gates, cseq, hlast, N, T};
-  const dim3 grid((unsigned)((N + kRows - 1) / kRows));
-#define TDE_LSTM_FWD(n) lstm_fwd_kernel<n><<<grid, 64 * n, 0, stream>>>(a)
-  TDE_LSTM_DISPATCH(TDE_LSTM_FWD)
-#undef TDE_LSTM_FWD
+  const FwdArgs<false> a = {{{z, u, hseq, hprev, gates, cseq, hlast}}, N, T, units};
+  launch_fwd(a, units, stream);
   TDE_LAUNCH_CHECK();
   return 0;
 }
@@ -311,23 +366,40 @@ TDE_API int tde_lstm32_fwd(const float* z, const float* u, float* hseq, float* h
 // [N, units] for the last step only with last_only)
 TDE_API int tde_lstm32_bwd(const float* gates, const float* cseq, const float* u, const float* dh, float* dz, int N,
                            int T, int units, int last_only, hipStream_t stream) {
-  if (!geo_ok(N, T, units)) return -1;
+  if (!geo_ok(N, T, units, units)) return -1;
   if (!gates || !cseq || !u || !dh || !dz) return -2;
-  const BwdArgs a = {gates, cseq, u, dh, dz, N, T, last_only};
-  const dim3 grid((unsigned)((N + kRows - 1) / kRows));
-  const int lds = 2 * kRows * 4 * units * (int)sizeof(float);   // 64 KiB at the upper end
-  static bool attr_set = false;
-  if (!attr_set) {
-#define TDE_LSTM_ATTR(n) \
-  (void)hipFuncSetAttribute((const void*)lstm_bwd_kernel<n>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kRows * 64 * n * 4)
-    TDE_LSTM_ATTR(1); TDE_LSTM_ATTR(2); TDE_LSTM_ATTR(3); TDE_LSTM_ATTR(4);
-    TDE_LSTM_ATTR(5); TDE_LSTM_ATTR(6); TDE_LSTM_ATTR(7); TDE_LSTM_ATTR(8);
-#undef TDE_LSTM_ATTR
-    attr_set = true;
-  }
-#define TDE_LSTM_BWD(n) lstm_bwd_kernel<n><<<grid, 64 * n, lds, stream>>>(a)
-  TDE_LSTM_DISPATCH(TDE_LSTM_BWD)
-#undef TDE_LSTM_BWD
+  const BwdArgs<false> a = {{{gates, cseq, u, dh, dz}}, N, T, last_only};
+  launch_bwd(a, units, stream);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// Both directions of a bidirectional layer in one launch.  Direction d (0: forward in time, 1: backward in time)
+// has its own Z_d, U_d and saved tensors hprev_d, gates_d, cseq_d.  seq: every h into out [N, T, 2 units], columns
+// d units .. of position t in the original time order (hseq_d unused).  Otherwise: the directions' final states into
+// out [N, 2 units], and every h into hseq_d [N, T, units] unless null.
+TDE_API int tde_lstm32_bi_fwd(const float* z0, const float* z1, const float* u0, const float* u1, float* hseq0,
+                              float* hseq1, float* hprev0, float* hprev1, float* gates0, float* gates1, float* cseq0,
+                              float* cseq1, float* out, int N, int T, int units, int seq, hipStream_t stream) {
+  if (!geo_ok(N, T, units, 2 * units)) return -1;
+  if (!z0 || !z1 || !u0 || !u1 || !hprev0 || !hprev1 || !gates0 || !gates1 || !cseq0 || !cseq1 || !out) return -2;
+  const FwdArgs<true> a = {{{z0, u0, seq ? out : hseq0, hprev0, gates0, cseq0, seq ? nullptr : out},
+                            {z1, u1, seq ? out + units : hseq1, hprev1, gates1, cseq1, seq ? nullptr : out + units}},
+                           N, T, seq ? 2 * units : units};
+  launch_fwd(a, units, stream);
+  TDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// dZ_d [N, T, 4 units] of both directions from the upstream dh [N, T, 2 units] (or [N, 2 units] with last_only: the
+// gradient of the final states), direction d reading columns d units ..
+TDE_API int tde_lstm32_bi_bwd(const float* gates0, const float* gates1, const float* cseq0, const float* cseq1,
+                              const float* u0, const float* u1, const float* dh, float* dz0, float* dz1, int N, int T,
+                              int units, int last_only, hipStream_t stream) {
+  if (!geo_ok(N, T, units, 2 * units)) return -1;
+  if (!gates0 || !gates1 || !cseq0 || !cseq1 || !u0 || !u1 || !dh || !dz0 || !dz1) return -2;
+  const BwdArgs<true> a = {{{gates0, cseq0, u0, dh, dz0}, {gates1, cseq1, u1, dh + units, dz1}}, N, T, last_only};
+  launch_bwd(a, units, stream);
   TDE_LAUNCH_CHECK();
   return 0;
 }

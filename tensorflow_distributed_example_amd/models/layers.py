@@ -1001,6 +1001,63 @@ class GRU(Layer):
                     **_reg_config(self, "kernel_regularizer", "recurrent_regularizer", "bias_regularizer"))
 
 
+class Bidirectional(Layer):
+    """Keras ``Bidirectional`` around an ``LSTM`` or ``GRU`` of this module, ``merge_mode="concat"``: the wrapped
+    recurrence over the sequence as it is and a second one, with weights of its own, over the reversed sequence;
+    [N, T, 2u] with the wrapped layer's ``return_sequences`` (both halves in the original time order), else the two
+    final states [N, 2u].  The weights are the wrapped layer's specs twice, under Keras's nested names
+    ``forward_<inner>/<cell>/kernel`` ... and ``backward_<inner>/...``; initializers, regularizers, ``use_bias`` and
+    ``unit_forget_bias`` are the wrapped layer's.  Other merge modes, ``backward_layer=``, ``weights=``, other wrapped
+    layers, masks and initial state are refused.  On the GPU: two 1x1 GEMM stages and ONE launch per sweep for both
+    directions (the BI kernels of csrc/kernels/lstm.hip / gru.hip), each writing its half of the output in place
+    (float32 policy)."""
+    _prefix = "bidirectional"
+
+    def __init__(self, layer, merge_mode="concat", weights=None, backward_layer=None, **kw):
+        super().__init__(**kw)
+        if isinstance(layer, dict):   # a nested config
+            layer = from_config(layer["class_name"], layer["config"])
+        for arg, val, ok in (("layer", layer, type(layer) in (LSTM, GRU) and not layer.built),
+                             ("merge_mode", merge_mode, merge_mode == "concat"),
+                             ("backward_layer", backward_layer, backward_layer is None),
+                             ("weights", weights, weights is None)):
+            if not ok:
+                raise NotImplementedError(f"{self.name} (Bidirectional): {arg}={val!r} is not supported: an unbuilt "
+                                          "LSTM or GRU of this package, merge_mode='concat', weights of its own")
+        self.layer, self.merge_mode = layer, merge_mode
+        self.units, self.use_bias, self.return_sequences = layer.units, layer.use_bias, layer.return_sequences
+        self.cell = f"{layer._prefix}_cell"
+        self.prefixes = (f"forward_{layer.name}", f"backward_{layer.name}")   # direction 0, direction 1
+
+    def __call__(self, inputs, mask=None, training=None, initial_state=None):
+        for arg, val in (("mask", mask), ("initial_state", initial_state)):
+            if val is not None:
+                raise NotImplementedError(f"{self.name} (Bidirectional): {arg}= is not supported: whole sequences "
+                                          "from a zero state only")
+        return super().__call__(inputs)
+
+    def build(self, input_shape):
+        self.layer.build(input_shape)
+        for pre in self.prefixes:
+            for s in self.layer.weight_specs:
+                self.weight_specs.append(WeightSpec(f"{pre}/{s.name}", s.shape, s.initializer,
+                                                    s.trainable and self.trainable, s.aggregation, self, s.l1, s.l2))
+        self.built = True
+
+    def compute_output_shape(self, s):
+        return (s[0], 2 * self.units) if self.return_sequences else (2 * self.units,)
+
+    def ref_call(self, x, W, training, rng=None, state_updates=None):
+        fw, bw = ({k[len(pre) + 1:]: v for k, v in W.items() if k.startswith(pre + "/")} for pre in self.prefixes)
+        a = self.layer.ref_call(x, fw, training)
+        b = self.layer.ref_call(torch.flip(x, [1]), bw, training)
+        return torch.cat([a, torch.flip(b, [1]) if self.return_sequences else b], dim=-1)
+
+    def get_config(self):   # ``from_config`` hands the nested config back to the constructor as ``layer``
+        return dict(name=self.name, merge_mode=self.merge_mode,
+                    layer={"class_name": type(self.layer).__name__, "config": self.layer.get_config()})
+
+
 class Embedding(Layer):
     """Keras ``Embedding``: integer ids [N, T] -> [N, T, output_dim], rows of the one variable ``embeddings``
     [input_dim, output_dim].  Ids arrive as the model input (float32 on the device, truncated toward zero as Keras
@@ -1234,7 +1291,7 @@ class RandomZoom(_RandomAffine):
 LAYER_CLASSES = {c.__name__: c for c in [InputLayer, Conv2D, DepthwiseConv2D, SeparableConv2D, Dense, MaxPooling2D, AveragePooling2D,
                                          GlobalAveragePooling2D, GlobalAveragePooling1D, ZeroPadding2D, Flatten, Reshape, Activation, ReLU,
                                          Dropout, BatchNormalization, GroupNormalization,
-                                         LayerNormalization, MultiHeadAttention, LSTM, GRU, Embedding, Add,
+                                         LayerNormalization, MultiHeadAttention, LSTM, GRU, Bidirectional, Embedding, Add,
                                          RandomFlip,
                                          RandomTranslation, RandomRotation, RandomZoom]}
 

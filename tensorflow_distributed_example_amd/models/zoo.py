@@ -193,6 +193,27 @@ def text_gru(vocab=2000, seq_len=32, dim=32, classes=4, name=None):
     ], name=name)
 
 
+def text_bilstm(vocab=2000, seq_len=32, dim=32, classes=4, name=None):
+    """The standard Keras text classifier: token ids -> Embedding -> Bidirectional(LSTM(64)) -> Dense (both
+    directions in one resident launch per sweep; csrc/kernels/lstm.hip)."""
+    return Sequential([
+        L.Embedding(vocab, dim, input_length=seq_len),
+        L.Bidirectional(L.LSTM(64)),
+        L.Dense(classes),
+    ], name=name)
+
+
+def text_bigru(vocab=2000, seq_len=32, dim=32, classes=4, name=None):
+    """Two stacked Bidirectional(GRU(64)), the first returning its sequence: the second sees 128 features and its
+    two projections' input gradients meet in one tensor (csrc/kernels/gru.hip)."""
+    return Sequential([
+        L.Embedding(vocab, dim, input_length=seq_len),
+        L.Bidirectional(L.GRU(64, return_sequences=True)),
+        L.Bidirectional(L.GRU(64)),
+        L.Dense(classes),
+    ], name=name)
+
+
 def with_input_stage(model, stage, name=None):
     """A Sequential of this module rebuilt (fresh layers, same names, new weights) behind the input stage
     ``stage``: a list of RandomFlip / RandomTranslation / RandomRotation / RandomZoom layers.  The input becomes the image itself: a model

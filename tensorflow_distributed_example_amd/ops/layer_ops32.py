@@ -52,6 +52,14 @@ N.register_hip({
     # csrc/kernels/gru.hip
     "tde_gru32_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),   # x, U, rb, hseq, hprev, acts, hlast, B, T, u
     "tde_gru32_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),    # acts, hprev, U, dh, dx, dr, B, T, u, last_only
+    # both directions of a Bidirectional in one launch: operand pairs (direction 0, direction 1), then out / dh
+    # z, U, hseq, hprev, gates, cseq pairs, out, B, T, u, seq
+    "tde_lstm32_bi_fwd": (_i, [_vp] * 13 + [_i, _i, _i, _i, _vp]),
+    "tde_lstm32_bi_bwd": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),    # gates, cseq, U pairs, dh, dz pair, B, T, u, last_only
+    # x, U, rb, hseq, hprev, acts pairs, out, B, T, u, seq
+    "tde_gru32_bi_fwd": (_i, [_vp] * 13 + [_i, _i, _i, _i, _vp]),
+    # acts, hprev, U pairs, dh, dx pair, dr pair, B, T, u, last_only
+    "tde_gru32_bi_bwd": (_i, [_vp] * 11 + [_i, _i, _i, _i, _vp]),
     # csrc/kernels/embedding.hip
     "tde_embed32_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),   # ids, table, out, n, V, D, ids_are_int
     "tde_embed32_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),   # ids, dy, dtable, n, V, D, ids_are_int
@@ -440,6 +448,65 @@ def gru_bwd(acts, hprev, rk, dh, dx, dr, B, T, units, last_only):
         _f32(t, k, f"gru_bwd {what}")
     N.check(N.hip().tde_gru32_bwd(_P(acts), _P(hprev), _P(rk), _P(dh), _P(dx), _P(dr), B, T, units,
                                   int(bool(last_only)), _s()), "tde_gru32_bwd")
+
+
+# ---------------------------------------------------------------- Bidirectional(LSTM | GRU): one launch per sweep
+# Every per-direction operand is a pair (direction 0: forward in time, direction 1: backward in time).  ``out`` is the
+# layer's output: with ``seq`` [B, T, 2 units], direction d's h of position t in columns d * units .. (original time
+# order; the ``hseq`` pair is not used and may be None); otherwise [B, 2 units], direction 0's state after t = T - 1
+# and direction 1's after t = 0, with every h into ``hseq[d]`` [B, T, units] when given.  ``hprev[d]`` at position t is
+# direction d's state before it processed position t: for direction 1 that is h of position t + 1, zeros at T - 1.
+def _pair(ts, n, what, optional=False):
+    _req(isinstance(ts, (tuple, list)) and len(ts) == 2, f"{what}: a pair (direction 0, direction 1) expected")
+    for d, t in enumerate(ts):
+        if t is not None or not optional:
+            _f32(t, n, f"{what}[{d}]")
+    return _P(ts[0]), _P(ts[1])
+
+
+def lstm_bi_fwd(z, rk, hseq, hprev, gates, cseq, out, B, T, units, seq):
+    """``lstm_fwd`` for both directions at once (grid (ceil(B / 16), 2)): see the section comment."""
+    n = lstm_check(B, T, units, "lstm_bi_fwd")
+    args = (*_pair(z, 4 * n, "lstm_bi_fwd z"), *_pair(rk, 4 * units * units, "lstm_bi_fwd recurrent kernel"),
+            *_pair(hseq or (None, None), n, "lstm_bi_fwd hseq", optional=True), *_pair(hprev, n, "lstm_bi_fwd hprev"),
+            *_pair(gates, 4 * n, "lstm_bi_fwd gates"), *_pair(cseq, n, "lstm_bi_fwd cseq"))
+    _f32(out, 2 * n if seq else 2 * B * units, "lstm_bi_fwd out")
+    N.check(N.hip().tde_lstm32_bi_fwd(*args, _P(out), B, T, units, int(bool(seq)), _s()), "tde_lstm32_bi_fwd")
+
+
+def lstm_bi_bwd(gates, cseq, rk, dh, dz, B, T, units, last_only):
+    """``lstm_bwd`` for both directions at once: dz[d] [B, T, 4 units] under dh [B, T, 2 units], or [B, 2 units]
+    with ``last_only`` (the gradient of the two final states).  One launch, no atomics: bitwise reproducible."""
+    n = lstm_check(B, T, units, "lstm_bi_bwd")
+    args = (*_pair(gates, 4 * n, "lstm_bi_bwd gates"), *_pair(cseq, n, "lstm_bi_bwd cseq"),
+            *_pair(rk, 4 * units * units, "lstm_bi_bwd recurrent kernel"))
+    _f32(dh, 2 * B * units if last_only else 2 * n, "lstm_bi_bwd dh")
+    N.check(N.hip().tde_lstm32_bi_bwd(*args, _P(dh), *_pair(dz, 4 * n, "lstm_bi_bwd dz"), B, T, units,
+                                      int(bool(last_only)), _s()), "tde_lstm32_bi_bwd")
+
+
+def gru_bi_fwd(x, rk, rb, hseq, hprev, acts, out, B, T, units, seq):
+    """``gru_fwd`` for both directions at once (grid (ceil(B / 16), 2)): see the section comment.  ``rb``: the pair
+    of recurrent biases [3 units], or None for none."""
+    n = gru_check(B, T, units, "gru_bi_fwd")
+    args = (*_pair(x, 3 * n, "gru_bi_fwd x"), *_pair(rk, 3 * units * units, "gru_bi_fwd recurrent kernel"),
+            *_pair(rb or (None, None), 3 * units, "gru_bi_fwd recurrent bias", optional=True),
+            *_pair(hseq or (None, None), n, "gru_bi_fwd hseq", optional=True), *_pair(hprev, n, "gru_bi_fwd hprev"),
+            *_pair(acts, 4 * n, "gru_bi_fwd acts"))
+    _f32(out, 2 * n if seq else 2 * B * units, "gru_bi_fwd out")
+    N.check(N.hip().tde_gru32_bi_fwd(*args, _P(out), B, T, units, int(bool(seq)), _s()), "tde_gru32_bi_fwd")
+
+
+def gru_bi_bwd(acts, hprev, rk, dh, dx, dr, B, T, units, last_only):
+    """``gru_bwd`` for both directions at once: dx[d] and dr[d] [B, T, 3 units] under dh [B, T, 2 units], or
+    [B, 2 units] with ``last_only``.  One launch, no atomics: bitwise reproducible."""
+    n = gru_check(B, T, units, "gru_bi_bwd")
+    args = (*_pair(acts, 4 * n, "gru_bi_bwd acts"), *_pair(hprev, n, "gru_bi_bwd hprev"),
+            *_pair(rk, 3 * units * units, "gru_bi_bwd recurrent kernel"))
+    _f32(dh, 2 * B * units if last_only else 2 * n, "gru_bi_bwd dh")
+    N.check(N.hip().tde_gru32_bi_bwd(*args, _P(dh), *_pair(dx, 3 * n, "gru_bi_bwd dx"),
+                                     *_pair(dr, 3 * n, "gru_bi_bwd dr"), B, T, units, int(bool(last_only)), _s()),
+            "tde_gru32_bi_bwd")
 
 
 # ---------------------------------------------------------------- Embedding (csrc/kernels/embedding.hip)

@@ -286,6 +286,25 @@ class LayerwisePlan(PG.ReplicaPlan):
                                     names=("gru_cell/kernel", "gru_cell/bias"), bias_row=0))
                 stages.append(_Gru(self, layer, z, tout))
                 continue
+            if isinstance(layer, L.Bidirectional):
+                # one projection stage per direction (both read x: their input gradients meet in x.grad by the
+                # multi-consumer rule, as an attention's Q, K, V), then ONE stage for both recurrences
+                who = f"{layer.name} (Bidirectional)"
+                if not self.f32:
+                    raise Unsupported(f"{who}: the recurrence kernels are float32 only; the mixed_bfloat16 policy "
+                                      "has none")
+                gru = isinstance(layer.layer, L.GRU)
+                zs = []
+                for pre in layer.prefixes:
+                    z = _T(max(T) + 1, (tin[0].shape[0], (3 if gru else 4) * layer.units))
+                    z.producer, z.consumers = i, [i]
+                    T[z.id] = z
+                    zs.append(z)
+                    stages.append(_Gemm(self, layer, tin[0], z, False, pointwise=True,
+                                        names=(f"{pre}/{layer.cell}/kernel", f"{pre}/{layer.cell}/bias"),
+                                        bias_row=0 if gru else None))
+                stages.append(_BiRnn(self, layer, zs, tout))
+                continue
             if isinstance(layer, L.Embedding):
                 # the ids are the model input, read from the bound input buffer (csrc/kernels/embedding.hip)
                 who = f"{layer.name} (Embedding)"
@@ -1216,6 +1235,78 @@ class _Gru(_Stage):
             O32.act_bwd(self.dr, None, B * self.T, 3 * self.units, relu=False, dbias=self.grb)
 
 
+class _BiRnn(_Stage):
+    """Both recurrences of a Bidirectional(LSTM | GRU) — float32 forms only — over the two internal tensors that the
+    directions' projection stages wrote: ONE launch for the forward sweeps and ONE for the backward sweeps (the BI
+    kernels of csrc/kernels/lstm.hip / gru.hip, grid (ceil(B / 16), 2)).  Direction d writes its h into columns
+    d * units .. of the output tensor and reads the output gradient from there, so no flip, concat or split runs.
+    The stage owns what each direction saves, as ``_Lstm`` / ``_Gru`` do for one; hseq is saved by nobody (the
+    backward sweeps do not read it).  After the backward launch: per direction, dU = hprev^T dZ (dR for a GRU) as
+    one weight-gradient GEMM, and a GRU's recurrent bias gradient as the column sum of dR.  Geometry:
+    (B, T, units)."""
+
+    def __init__(self, plan, layer, zs, tout):
+        self.layer, self.zs, self.out = layer, zs, tout
+        self.inp = zs[0]
+        self.node_index = tout.producer
+        self.gru = isinstance(layer.layer, L.GRU)
+        self.G = 3 if self.gru else 4
+        self.T, self.units, self.seq = zs[0].shape[0], layer.units, layer.return_sequences
+        try:
+            O32.lstm_check(*self.geom(plan.B), f"{layer.name} (Bidirectional)")
+        except ValueError as e:
+            raise Unsupported(str(e)) from None
+        st = plan.store
+        self.unames = [f"{layer.name}/{pre}/{layer.cell}/recurrent_kernel" for pre in layer.prefixes]
+        self.U = [st.view(n) for n in self.unames]
+        self.gU = [st.grad(n) for n in self.unames]
+        self.bnames = ([f"{layer.name}/{pre}/{layer.cell}/bias" for pre in layer.prefixes]
+                       if self.gru and layer.use_bias else None)
+        self.rb = [st.view(n)[1] for n in self.bnames] if self.bnames else None
+        self.grb = [st.grad(n).view(2, -1)[1] for n in self.bnames] if self.bnames else None
+
+    def geom(self, B):
+        return (B, self.T, self.units)
+
+    def param_names(self):
+        return list(self.unames)
+
+    def alloc(self, B, dev):
+        n = B * self.T * self.units
+
+        def pair(k):
+            return [torch.zeros(k * n, dtype=torch.float32, device=dev) for _ in range(2)]
+
+        self.hprev, self.acts = pair(1), pair(4)    # acts: an LSTM's gates; a GRU's z, r, hh, R_h
+        self.cseq = None if self.gru else pair(1)
+        self.dr = pair(3) if self.gru else None
+
+    def wpart_need(self, B):
+        return O32.wgrad_part_elems(self.units, self.G * self.units, B * self.T)
+
+    def grad_inputs(self):
+        return list(self.zs)
+
+    def fwd(self, p, B, training, mode="train"):
+        z, out = [t.root().buf for t in self.zs], self.out.root().buf
+        if self.gru:
+            O32.gru_bi_fwd(z, self.U, self.rb, None, self.hprev, self.acts, out, *self.geom(B), seq=self.seq)
+        else:
+            O32.lstm_bi_fwd(z, self.U, None, self.hprev, self.acts, self.cseq, out, *self.geom(B), seq=self.seq)
+
+    def bwd(self, p, B):
+        dz = [t.root().grad for t in self.zs]   # each has this one consumer: written, never accumulated
+        dh = self.out.root().grad
+        if self.gru:
+            O32.gru_bi_bwd(self.acts, self.hprev, self.U, dh, dz, self.dr, *self.geom(B), last_only=not self.seq)
+        else:
+            O32.lstm_bi_bwd(self.acts, self.cseq, self.U, dh, dz, *self.geom(B), last_only=not self.seq)
+        for d, dzu in enumerate(self.dr if self.gru else dz):
+            O32.dense_wgrad(self.hprev[d], dzu, self.gU[d].view(self.units, -1), B * self.T, part=p.wpart)
+            if self.grb is not None:
+                O32.act_bwd(dzu, None, B * self.T, 3 * self.units, relu=False, dbias=self.grb[d])
+
+
 class _Embedding(_Stage):
     """An Embedding on csrc/kernels/embedding.hip — float32 forms only.  The ids are the model input itself: the
     forward reads the bound input buffer (the ring slot, float32 ids truncated by the kernel), so it has no
@@ -1501,6 +1592,18 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
     def get(t):
         return vals[t.root().id].reshape((B,) + t.shape)
 
+    def lstm_loop(zz, Uk, seq):
+        """The LSTM step loop over the projected input zz [B, T, 4u] from a zero state."""
+        u = Uk.shape[0]
+        h = c = zz.new_zeros(zz.shape[0], u)
+        hs = []
+        for t in range(zz.shape[1]):
+            gi, gf, gg, go = (zz[:, t] + h @ Uk).split(u, dim=-1)
+            c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+            h = torch.sigmoid(go) * torch.tanh(c)
+            hs.append(h)
+        return torch.stack(hs, 1) if seq else h
+
     moving = {}
     loss = None
     for stg in plan.stages:
@@ -1537,19 +1640,20 @@ def emulate_step(plan: LayerwisePlan, x, y, B=None):
             pr = torch.softmax(q @ k.transpose(-1, -2) / dk ** 0.5, dim=-1)
             vals[stg.out.root().id] = (pr @ v).transpose(1, 2).reshape(B, -1)
         elif isinstance(stg, _Lstm):
-            _, T_, u = stg.geom(B)
-            zz, Uk = get(stg.inp), W[stg.uname]
-            h = c = zz.new_zeros(B, u)
-            hs = []
-            for t in range(T_):
-                gi, gf, gg, go = (zz[:, t] + h @ Uk).split(u, dim=-1)
-                c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
-                h = torch.sigmoid(go) * torch.tanh(c)
-                hs.append(h)
-            vals[stg.out.root().id] = (torch.stack(hs, 1) if stg.seq else h).reshape(B, -1)
+            vals[stg.out.root().id] = lstm_loop(get(stg.inp), W[stg.uname], stg.seq).reshape(B, -1)
         elif isinstance(stg, _Gru):
             rb = W[stg.bname][1] if stg.bname else None
             vals[stg.out.root().id] = L.GRU.recurrence(get(stg.inp), W[stg.uname], rb, stg.seq).reshape(B, -1)
+        elif isinstance(stg, _BiRnn):   # direction 1: the same loop on the flipped projection, flipped back
+            halves = []
+            for d, (zt, un) in enumerate(zip(stg.zs, stg.unames)):
+                zz = torch.flip(get(zt), [1]) if d else get(zt)
+                if stg.gru:
+                    hh = L.GRU.recurrence(zz, W[un], W[stg.bnames[d]][1] if stg.bnames else None, stg.seq)
+                else:
+                    hh = lstm_loop(zz, W[un], stg.seq)
+                halves.append(torch.flip(hh, [1]) if d and stg.seq else hh)
+            vals[stg.out.root().id] = torch.cat(halves, -1).reshape(B, -1)
         elif isinstance(stg, _Elementwise):
             a = get(stg.inp)
             if stg.drop.rate > 0:
